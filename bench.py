@@ -29,6 +29,15 @@ of target / weight / damping, replicated BA: STRONG scaling — is measured in t
 and reported under "strong_scaling_config5" (N > 1) / extra.config5_backend_n1 (N = 1).
 The per-BA-step all-gather alone is also timed ("exchange").
 
+Plain run (the default): set up, warm up, time the --steps steps, print the line.  `value`, `ms_per_step` and
+`config` are the headline; `roofline` and `cpu_baseline` are null.  Everything else above — the roofline with its
+block-median device time, `extra`, the config-5 leg, the exchange timing, the CPU baselines — takes runs of its own
+and is measured only with --full.
+
+--dump-outputs DIR: after the timed steps, write what the timed path computed in its last step (the arrays a caller of
+that path receives) as DIR/<name>.npy in float32 / float64; above DUMP_BUDGET_BYTES in all, a fixed seeded sample of
+each.  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -45,6 +54,28 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: total .npy payload (the cap is 64 MB)
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(outdir, arrays):
+    """Write `arrays` (name -> tensor / ndarray) as outdir/<name>.npy: float64 stays float64, every other dtype becomes
+    float32.  When their total exceeds DUMP_BUDGET_BYTES, each array is replaced by the same fixed seeded sample of its
+    flattened elements (sorted indices; the share of the budget in proportion to its size), so that the files of two
+    runs with the same arguments hold the same elements."""
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            flat = a.reshape(-1)
+            k = max(1, flat.size * DUMP_BUDGET_BYTES // total)
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.size, size=k))
+            a = flat[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def make_inputs(E, H1, W1, L, radius, seed, device, from_fmaps=True):
@@ -174,12 +205,13 @@ def dry_run_cpu(args, rank, world):
         t = torch.tensor([wall], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if world > 1 and args.full:
         mine = torch.randn(E, H1, W1, 4)
         allv = torch.empty(world * E, H1, W1, 4)
         dist.all_gather_into_tensor(allv, mine)
         exchange = {"op": "all_gather(target,weight) over gloo (dry run)", "bytes_per_rank": mine.numel() * 4, "ms": 0.0}
     strong = None
-    if not args.no_backend:
+    if args.full and not args.no_backend:
         # the config-5 leg's control flow: fixed edge list, source-frame chunks dealt to the ranks, exchanged, agreement checked
         import lgu_slam_amd
         sh = lgu_slam_amd.sharded
@@ -466,16 +498,19 @@ def lowmem_main(args, ops, dev, rank, world, use_dist):
     ev1.record()
     barrier()
     wall = time.perf_counter() - t0
-    dev_ms = ev0.elapsed_time(ev1)
     if use_dist:
         import torch.distributed as dist
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"corr": out})
     if rank == 0:
-        blocks = time_blocks(lambda i: plan(coords, out=out), args.steps, args.blocks)
-        roof = lowmem_roofline(S, float(np.median(blocks)))
-        roof["device_ms_per_step_blocks"] = blocks
+        roof = None
+        if args.full:
+            blocks = time_blocks(lambda i: plan(coords, out=out), args.steps, args.blocks)
+            roof = lowmem_roofline(S, float(np.median(blocks)))
+            roof["device_ms_per_step_blocks"] = blocks
         res = {"metric": "def-corr-sample Mpix·edges/s (60×80 fmap, on-the-fly correlation, r=3, L=4)",
                "value": n_ranks * units / (wall / args.steps) / 1e6, "unit": "Mpix·edges/s", "n_gpus": n_ranks, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": wall * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -485,7 +520,7 @@ def lowmem_main(args, ops, dev, rank, world, use_dist):
                                       "target maps chunk-planar as AltCorrBlock stores them" % S["B"],
                           "edges_per_gpu": S["B"], "units_per_step_per_gpu": units, "sharding": "edges (no data-path collective)"},
                "roofline": roof,
-               "cpu_baseline": None if (args.no_cpu or world > 1) else lowmem_cpu_baseline(S)}
+               "cpu_baseline": None if (args.no_cpu or world > 1 or not args.full) else lowmem_cpu_baseline(S)}
         emit(res)
     if use_dist:
         import torch.distributed as dist
@@ -495,7 +530,10 @@ def lowmem_main(args, ops, dev, rank, world, use_dist):
 
 def backend_main(args, lgu, dev, rank, world, use_dist):
     """--workload backend: the config-5 step as the whole run's line."""
-    res = backend_run(args, lgu, dev, rank, world, use_dist, args.steps, args.warmup)
+    outputs = {}
+    res = backend_run(args, lgu, dev, rank, world, use_dist, args.steps, args.warmup, outputs)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         emit(res)
     if use_dist:
@@ -504,7 +542,7 @@ def backend_main(args, lgu, dev, rank, world, use_dist):
         dist.destroy_process_group()
 
 
-def backend_run(args, lgu, dev, rank, world, use_dist, steps, warmup):
+def backend_run(args, lgu, dev, rank, world, use_dist, steps, warmup, outputs=None):
     """BASELINE config 5: one global-BA iteration of update_lowmem (reference factor_graph.py:256-302) over a ~2000-edge
     factor graph (200 keyframes of 60x80x128 half feature maps, edges between frames at most 5 apart = 1970 edges),
     STRONG scaling: the graph is fixed and its source-frame chunks are dealt round-robin to the ranks.  One step =
@@ -514,7 +552,8 @@ def backend_run(args, lgu, dev, rank, world, use_dist, steps, warmup):
       exchange  all-gather of target / weight by edge and of damping by source frame (RCCL)
       ba        dense bundle adjustment, 2 iterations, replicated on every rank (parity unpinned, experimental)
     `value` = pixel·edges of the WHOLE graph per second of step time (max over ranks).
-    Every rank calls this (it issues collectives); returns the record on rank 0, None elsewhere."""
+    Every rank calls this (it issues collectives); returns the record on rank 0, None elsewhere.  `outputs` (a dict):
+    filled with what the last timed step left for the caller (poses and disparities after BA, target, weight, damping)."""
     import torch.distributed as dist
     sh = lgu.sharded
     n_ranks = dist.get_world_size() if use_dist else 1
@@ -644,6 +683,8 @@ def backend_run(args, lgu, dev, rank, world, use_dist, steps, warmup):
     barrier()
     wall = time.perf_counter() - t0
     gc.unfreeze()
+    if outputs is not None:
+        outputs.update(poses=poses, disps=disps, target=target, weight=weight, damping=damping)
     agree = sh.replicas_agree(poses, disps, target, weight, damping) if use_dist and (world > 1 or sh.REHEARSE_COLLECTIVES) else True
     if use_dist:
         t = torch.tensor([wall] + [float(np.median(phase[k])) for k in ("lookups", "exchange", "ba", "update_standin")] +
@@ -754,8 +795,13 @@ def main():
                                                              "them from one HIP graph")
     ap.add_argument("--randn-volumes", action="store_true", help="N(0,1) volumes instead of fmap products")
     ap.add_argument("--no-backend", action="store_true", help="skip the BASELINE config-5 leg (one sharded global-BA iteration, strong "
-                    "scaling) that the default workload reports beside the headline")
+                    "scaling) that the default workload reports beside the headline with --full")
     ap.add_argument("--backend-steps", type=int, default=8, help="timed steps of the config-5 leg inside the default workload")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the roofline "
+                    "(block-median device time, algorithmic bytes, PMC traffic), 'extra', the config-5 leg, the exchange "
+                    "timing and the CPU baselines (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in "
+                    "its last step as DIR/<name>.npy (float32 / float64, a fixed seeded sample above 60 MiB in all)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="TEST ONLY: exercise the launch / process-group / timing / JSON logic with gloo on CPU and an "
                          "empty step (no kernel runs, the printed value is meaningless)")
@@ -802,7 +848,7 @@ def main():
     E, H1, W1, L, R = args.edges, 48, 64, 4, 3
     cold = args.cache == "cold"
     tiled = args.layout == "tiled"
-    want_extra = rank == 0 and world == 1 and not args.no_extra
+    want_extra = args.full and rank == 0 and world == 1 and not args.no_extra
     # what CorrBlock.__init__ (ops.volume_pyramid(tiled=True)) leaves in HBM; building it is setup, not timed
     sets = DefcorrSets(ops, E, args.sets if cold else 1, 1234 + rank, dev, args.randn_volumes,
                        keep_rowmajor=(not tiled) or want_extra)
@@ -853,9 +899,11 @@ def main():
         n_ranks = dist.get_world_size()   # the ranks RCCL actually initialised
     ms_per_step = wall * 1e3 / args.steps
     value = n_ranks * units / (wall / args.steps) / 1e6
+    if rank == 0 and args.dump_outputs:   # before anything else reuses the output buffer
+        dump_outputs(args.dump_outputs, {"corr": out})
 
     exchange = None
-    if use_dist:  # the sharded driver's per-BA-step all-gather of target+weight (E,ht,wd,2)x2
+    if use_dist and args.full:  # the sharded driver's per-BA-step all-gather of target+weight (E,ht,wd,2)x2
         import torch.distributed as dist
         mine = torch.randn(E, H1, W1, 4, device=dev)
         allv = torch.empty(world * E, H1, W1, 4, device=dev)
@@ -876,7 +924,7 @@ def main():
     # BASELINE config 5 in the same run: the multi-GPU design proper (fixed graph, chunks dealt to the ranks, all-gathers,
     # BA) — STRONG scaling; every rank takes part (collectives)
     strong, strong_error = None, None
-    if not args.no_backend:
+    if args.full and not args.no_backend:
         try:
             strong = backend_run(args, lgu_slam_amd, dev, rank, world, use_dist, args.backend_steps, 3)
         except Exception as exc:   # the headline above is measured: a failure of this leg is reported in the line, not instead of it
@@ -885,20 +933,29 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        A, U = algorithmic_bytes_per_unit(sets.rowmajor[0], sets.coords[0], sets.offs[0], R)
-        A_planar = A
-        if args.out_format == "nhwc_f16":  # the output row is 2-byte elements
-            A -= L * (2 * R + 1) ** 2 * 2
-        kname = kernel_name(args.variant, args.probe, tiled, args.out_format)
-        traffic, traffic_src = (None, None)
-        if E == 20 and not args.probe and args.out_format == "planar":
-            traffic, traffic_src = load_traffic(kname, args.cache, tiled)
-        # headline device time: median over blocks of --steps launches in the headline's own mode (HIP events on the
-        # launch stream); the single timed region above gives `value` / `ms_per_step` per the driver contract
-        pre = sets.restore_offsets if args.probe else None
-        hb = time_blocks(step, min(args.steps, 16) if args.probe else args.steps, args.blocks, pre)
-        kern_ms = float(np.median(hb))
-        achieved = A * units / (kern_ms * 1e-3) / 1e9
+        roofline = None
+        if args.full:
+            A, U = algorithmic_bytes_per_unit(sets.rowmajor[0], sets.coords[0], sets.offs[0], R)
+            A_planar = A
+            if args.out_format == "nhwc_f16":  # the output row is 2-byte elements
+                A -= L * (2 * R + 1) ** 2 * 2
+            kname = kernel_name(args.variant, args.probe, tiled, args.out_format)
+            traffic, traffic_src = (None, None)
+            if E == 20 and not args.probe and args.out_format == "planar":
+                traffic, traffic_src = load_traffic(kname, args.cache, tiled)
+            # headline device time: median over blocks of --steps launches in the headline's own mode (HIP events on the
+            # launch stream); the single timed region above gives `value` / `ms_per_step` per the driver contract
+            pre = sets.restore_offsets if args.probe else None
+            hb = time_blocks(step, min(args.steps, 16) if args.probe else args.steps, args.blocks, pre)
+            kern_ms = float(np.median(hb))
+            achieved = A * units / (kern_ms * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch (PMC)",
+                        "traffic_source": traffic_src, "algorithmic_bytes_per_launch": A * units,
+                        "algorithmic_bytes_per_unit": A, "unique_volume_elements_per_unit": U,
+                        "kernel": kname, "cache": args.cache,
+                        "device_ms_per_step": kern_ms, "device_ms_per_step_blocks": hb,
+                        "device_ms_per_step_timed_region": dev_ms / args.steps}
         cache_note = ("cold: launches rotate over %d disjoint input sets (%d x ~255 MB of touched lines between two uses of a "
                       "line > 256 MiB Infinity Cache), every launch HBM-served" % (args.sets, args.sets - 1)) if cold else \
                      "warm: every launch re-reads the same inputs (touched set ~243 MiB can stay in the Infinity Cache)"
@@ -920,13 +977,7 @@ def main():
                        "pyramid_layout": "4x8-tiled slices (CorrBlock's own storage; results bit-identical)" if tiled
                                          else "row-major slices (reference operator layout)",
                        "out_format": args.out_format},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_unit": "bytes per launch (PMC)",
-                         "traffic_source": traffic_src, "algorithmic_bytes_per_launch": A * units,
-                         "algorithmic_bytes_per_unit": A, "unique_volume_elements_per_unit": U,
-                         "kernel": kname, "cache": args.cache,
-                         "device_ms_per_step": kern_ms, "device_ms_per_step_blocks": hb,
-                         "device_ms_per_step_timed_region": dev_ms / args.steps},
+            "roofline": roofline,
             "cpu_baseline": None,
         }
         res["config"]["library"] = lgu_slam_amd._lib.version()
@@ -948,7 +999,7 @@ def main():
                 res.setdefault("extra", {})["config5_backend_n1"] = keep
         if strong_error is not None:
             res["strong_scaling_config5" if n_ranks > 1 else "config5_backend_error"] = {"error": strong_error}
-        if not (args.no_cpu or world > 1):  # rank 0, N=1 only
+        if args.full and not (args.no_cpu or world > 1):  # rank 0, N=1 only
             res["cpu_baseline"] = cpu_baseline(E, H1, W1, L, R)
         if exchange:
             res["exchange"] = exchange

@@ -297,6 +297,62 @@ def head_functions_case(seed=5):
                 pcn3_in=n_(x3), pcn3_out=n_(ref_ga.per_Corr_Normalization(x3, [1, 2])))
 
 
+def direct_case(seed=77, head_seed=9, h=8, w=12, E=2):
+    """The reference's offset heads (CorrBlock.fpn_offset_generate, AltCorrBlock.offset_generate) and GaussianMask.forward
+    on fresh inputs, no scenario around them.  Only outputs are stored: the inputs and heads are drawn from the seeds,
+    which tests/test_glue_reference.py::test_reference_glue_functions_called_directly draws again.  The two offset
+    generators agree bit for bit (checked here), so their offsets are stored once."""
+    ref_corr, ref_ga = load_reference_glue()
+    g = torch.Generator().manual_seed(seed)
+    ofsMap, ofs_residual, ref_GA = make_heads(ref_ga, h, w, seed=head_seed)
+    feats = torch.randn((E, 256, h, w), generator=g) * 0.5
+    out = {}
+    with torch.no_grad():
+        holder = type("Holder", (), {})()
+        holder.ofsMap, holder.ofs_residual, holder.offset = ofsMap, ofs_residual, []
+        ref_corr.CorrBlock.fpn_offset_generate(holder, feats)
+        out.update({"offset%d" % l: n_(o) for l, o in enumerate(holder.offset)})
+        holder.offset = []
+        ref_corr.AltCorrBlock.offset_generate(holder, feats)
+        assert all(np.array_equal(out["offset%d" % l], n_(o)) for l, o in enumerate(holder.offset))
+        vol = torch.randn((E, h, w, h, w), generator=g)
+        ref_v, ref_mean, ref_det = ref_GA(feats.permute(0, 2, 3, 1).contiguous(), vol)
+        out.update(v=n_(ref_v), mean=n_(ref_mean), det=n_(ref_det), shape=np.array([E, h, w]))
+    return out
+
+
+def glue_surface():
+    """What the reference's corr.py / gaussianMask_cuda.py take from the extension modules and offer to their callers:
+    the modules each imports and the functions it calls on them (read from the module's syntax tree), the public classes
+    and functions, the constructor parameters of CorrBlock / AltCorrBlock and the parameter names of GaussianMask(4, 4)
+    (the keys a reference state dict carries).  Names only."""
+    import ast
+    import inspect
+    ref_corr, ref_ga = load_reference_glue()
+    ext = ("defCorrSample", "droid_backends")
+
+    def resolves(mod):
+        tree = ast.parse(open(mod.__file__).read())
+        calls = {m: set() for m in ext}
+        imported = set()
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Import):
+                imported.update(a.name for a in node.names if a.name in ext)
+            elif isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in ext:
+                calls[node.value.id].add(node.attr)
+        return {m: sorted(calls[m]) for m in sorted(imported)}
+
+    return {
+        "modules.corr": {"resolves": resolves(ref_corr),
+                         "public": ["CorrSampler", "DefCorrSampler", "CorrBlock", "AltCorrBlock", "per_Corr_Normalization"],
+                         "CorrBlock.__init__": list(inspect.signature(ref_corr.CorrBlock.__init__).parameters),
+                         "AltCorrBlock.__init__": list(inspect.signature(ref_corr.AltCorrBlock.__init__).parameters)},
+        "gaussianMask_cuda": {"resolves": resolves(ref_ga),
+                              "public": ["GaussianMask", "GaussianMaskCuda"],
+                              "GaussianMask(4, 4).named_parameters": sorted(dict(ref_ga.GaussianMask(4, 4).named_parameters()))},
+    }
+
+
 def main(outdir):
     os.makedirs(outdir, exist_ok=True)
     torch.set_num_threads(max(1, min(8, os.cpu_count() or 1)))
@@ -309,6 +365,12 @@ def main(outdir):
     _, ref_ga = load_reference_glue()
     save("glue_heads", heads_state(*make_heads(ref_ga, 16, 16)))    # the same seeded heads in every scenario
     save("glue_functions", head_functions_case())
+    save("glue_direct_8x12", direct_case())
+    import json
+    with open(os.path.join(outdir, "glue_surface.json"), "w") as fh:
+        json.dump(glue_surface(), fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote glue_surface.json")
     save("glue_corrblock_16x16", corrblock_scenario(16, 16, 2, 1, seed=101))
     save("glue_corrblock_48x64", corrblock_scenario(48, 64, 1, 1, seed=102, sub=(3, 4)))
     save("glue_altcorr_16x16", altcorr_scenario(16, 16, 4, [[(0, 1), (0, 2), (1, 0), (1, 1)], [(2, 3), (3, 0)]], seed=103))

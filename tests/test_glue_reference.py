@@ -135,33 +135,27 @@ def _gen():
     return mod
 
 
-@needs_ref
 def test_reference_glue_functions_called_directly(lgu):
-    """Fresh inputs through the reference's functions and this build's, side by side (no fixture in between)."""
+    """Fresh inputs (no scenario around them) through this build's functions against what the reference's own offset
+    heads (CorrBlock.fpn_offset_generate and AltCorrBlock.offset_generate: identical, one copy stored) and
+    GaussianMask.forward returned on them (glue_direct_8x12.npz, written by oracle/gen_glue_golden.py's direct_case,
+    which draws the inputs and heads from the seeds drawn again here)."""
     gen = _gen()
-    ref_corr, ref_ga = gen.load_reference_glue()
+    z = gold("glue_direct_8x12")
     g = torch.Generator().manual_seed(77)
-    h, w, E = 16, 24, 2
-    ofsMap, ofs_residual, ref_GA = gen.make_heads(ref_ga, h, w, seed=9)
-    GA = lgu.GaussianMask(h, w)
-    GA.load_state_dict(ref_GA.state_dict())
+    E, h, w = [int(v) for v in z["shape"]]
+    ofsMap, ofs_residual, GA = gen.make_heads(lgu.gaussian_mask, h, w, seed=9)   # same parameter names as the reference's
     feats = torch.randn((E, 256, h, w), generator=g) * 0.5
     with torch.no_grad():
-        holder = type("Holder", (), {})()
-        holder.ofsMap, holder.ofs_residual, holder.offset = ofsMap, ofs_residual, []
-        ref_corr.CorrBlock.fpn_offset_generate(holder, feats)
         offs, zero = lgu.corr.generate_offsets(ofsMap, ofs_residual, feats, 4)
         for l in range(4):
-            assert torch.equal(offs[l].contiguous(), holder.offset[l].contiguous()) or \
-                float((offs[l] - holder.offset[l]).abs().max()) <= 2e-6, "level %d" % l
-        holder.offset = []
-        ref_corr.AltCorrBlock.offset_generate(holder, feats)
-        for l in range(4):
-            assert float((offs[l] - holder.offset[l]).abs().max()) <= 2e-6
+            want = T(z["offset%d" % l])
+            assert tuple(offs[l].shape) == tuple(want.shape), "level %d" % l
+            assert torch.equal(offs[l].contiguous(), want) or float((offs[l] - want).abs().max()) <= 2e-6, "level %d" % l
         # Gaussian head: the reference's forward with the kernel call replaced by the oracle (stand-in module)
         vol = torch.randn((E, h, w, h, w), generator=g)
         x = feats.permute(0, 2, 3, 1).contiguous()
-        ref_v, ref_mean, ref_det = ref_GA(x, vol)
+        ref_v, ref_mean, ref_det = T(z["v"]), T(z["mean"]), T(z["det"])
         mean, cov, det = GA.gaussian_parameters(x)
         assert float((mean - ref_mean).abs().max()) <= 1e-5 and float((det - ref_det).abs().max()) <= 1e-5
         from oracle import oracle as O

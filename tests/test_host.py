@@ -5,6 +5,7 @@ world_size 2."""
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn as nn
@@ -180,7 +181,7 @@ def test_bench_distributed_control_flow_gloo_world2():
     port = 29600 + (os.getpid() % 1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--dry-run-cpu"]
+           "--warmup", "1", "--dry-run-cpu", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -205,7 +206,7 @@ def test_bench_launches_its_own_ranks_from_a_plain_command():
     print n_gpus 1): the parent starts the two ranks itself, relays rank 0's single JSON line, and the line's n_gpus is
     the number of ranks the process group initialised.  It also carries the config-5 strong-scaling leg's record."""
     import json
-    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-cpu"])
+    out = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run-cpu", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-500:]
@@ -214,15 +215,56 @@ def test_bench_launches_its_own_ranks_from_a_plain_command():
     sc = d["strong_scaling_config5"]
     assert sc["n_gpus"] == 2 and sc["replicas_agree"] and sc["every_edge_owned"] and min(sc["edges_per_rank"]) > 0
     # N = 1: no launcher, no process group, one line
-    one = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dry-run-cpu"])
+    one = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "0", "--dry-run-cpu", "--full"])
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
     assert d1["n_gpus"] == 1 and "exchange" not in d1 and d1["config5_backend_n1"]["n_gpus"] == 1
 
 
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full the line carries the headline and nothing that takes runs of its own: no config-5 leg, no exchange
+    timing, no roofline, no CPU baseline — at world size 1 and 2 alike."""
+    import json
+    for argv in (["--gpus", "1", "--steps", "4", "--warmup", "1", "--dry-run-cpu"],
+                 ["--gpus", "2", "--steps", "4", "--warmup", "1", "--dry-run-cpu"]):
+        out = _run_bench(argv)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and lines[0].startswith("{"), out.stdout[-500:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] >= 0 and d["n_gpus"] == int(argv[1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in d
+        assert "exchange" not in d and "strong_scaling_config5" not in d and "config5_backend_n1" not in d
+        assert d["roofline"] is None and d["cpu_baseline"] is None
+
+
+def test_bench_dump_outputs_dtypes_and_budget(tmp_path):
+    """--dump-outputs: float64 stays float64, other dtypes become float32; above the budget every array is replaced by
+    the same fixed sample of its elements, whatever run writes it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = {"a": torch.arange(12, dtype=torch.float16).view(3, 4), "b": np.arange(5, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    a, b = np.load(tmp_path / "small" / "a.npy"), np.load(tmp_path / "small" / "b.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 4) and np.array_equal(a, np.arange(12).reshape(3, 4))
+    assert b.dtype == np.float64 and np.array_equal(b, np.arange(5))
+    n = bench.DUMP_BUDGET_BYTES // 4 + 1000             # one float32 array just above the budget
+    big = {"x": torch.arange(n, dtype=torch.float32), "y": torch.ones(1000, dtype=torch.float64)}
+    for run in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    total = sum(os.path.getsize(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one"))
+    assert total <= 64 * 1000 * 1000
+    x1, x2 = np.load(tmp_path / "one" / "x.npy"), np.load(tmp_path / "two" / "x.npy")
+    assert x1.dtype == np.float32 and 0 < x1.size < n and np.array_equal(x1, x2)
+    assert np.all(np.diff(x1) > 0) and np.load(tmp_path / "one" / "y.npy").dtype == np.float64
+
+
 def test_bench_exits_nonzero_when_a_rank_fails():
     """A failing rank must fail the whole command (no line, non-zero status), whoever launched it."""
-    out = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--dry-run-cpu", "--edges", "-1"])
+    out = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--dry-run-cpu", "--full", "--edges", "-1"])
     assert out.returncode != 0 and not [l for l in out.stdout.splitlines() if l.startswith("{")]
     # and a launcher whose world disagrees with --gpus is refused instead of silently measuring something else
     import subprocess
