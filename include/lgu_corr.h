@@ -442,6 +442,40 @@ int lgu_ba_assemble_f64(const float* Hs, const long long* hptr, const long long*
 int lgu_ba_pose_retr_f32(float* poses, const float* dx, int t0, int t1, void* stream);
 int lgu_ba_disp_retr_f32(float* disps, const float* dz, const long long* inds, int n, int HW, void* stream);
 
+/* ---- geometry entries of droid_backends (reference src/droid.cpp:237-249) ---------------------------------------
+ * frame_distance, projmap, depth_filter and iproj of src/droid_kernels.cu.  poses (np,7) float = t, q(xyzw); disps
+ * (nd,ht,wd) float; intrinsics (>= 4 floats) = fx, fy, cx, cy; index arrays are int64 device arrays.  Per-pixel values
+ * follow the reference's fp32 operation order bit for bit.  A frame index is valid when 0 <= index < min(np, nd); no
+ * kernel dereferences an invalid one (the reference reads out of bounds).  Every output element is written (the
+ * reference's outputs are zero-filled first; these need no fill).  Launched on `stream`, no host synchronisation.
+ *
+ * lgu_frame_distance_f32  frame_distance_kernel (:518-658, host :1438-1460): dist[k] for the pair ii[k] -> jj[k]: per
+ *   pixel, the flow magnitude under T_ij (weight beta) and under its translation alone (weight 1 - beta); a weight
+ *   always counts to the total, to the valid weight and (times the magnitude) to the sum only where the point's depth
+ *   > 0.25.  dist = 1000 if valid / (total + 1e-8) < 0.75 (in double), else sum / valid.  The pixels of a pair are
+ *   summed in a fixed order that depends on (ht, wd) only: a pair's result does not depend on the batch it is in.
+ *   NaN for a pair with an invalid index.
+ * lgu_projmap_f32         projmap_kernel (:427-516, host :1463-1488): coords (num,ht,wd,3) = (u, v, 0), (u, v) replaced
+ *   by the projection into jj[k] where the depth > 0.01 (double comparison); valid (num,ht,wd,1) = depth > 0.25.  A pair
+ *   with an invalid index: coords (NaN, NaN, 0), valid 0.
+ * lgu_depth_filter_f32    depth_filter_kernel (:661-776, host :1491-1515): counter (num,ht,wd), for each pixel of frame
+ *   ix[b], the number of neighbours ix-1, ix-2, ix-3, ix+3, ix+4, ix+5 (valid ones only) in which the pixel projects
+ *   with floor(u) in [0, wd-1) and floor(v) in [0, ht-1) and |1/d_proj - 1/d_corner| < thresh[b] in double for one of
+ *   the four corners.  floor() converts to int as v_cvt_i32_f32 does (NaN -> 0, saturating).  A zero row for an
+ *   invalid ix[b].
+ * lgu_iproj_f32           iproj_kernel (:779-851, host :1518-1541): points (nd,ht,wd,3) = act_se3(poses[n], (x, y, 1, d))
+ *   divided by d; NaN points for frames n >= np.
+ * Sizes: num, np, nd, ht, wd >= 0 (num == 0 or an empty frame: nothing is launched), ht * wd < 2^31 / 3, otherwise
+ * LGU_E_BADARG; more than 65535 * 256 pixels per frame: LGU_E_UNSUPPORTED (projmap, depth_filter, iproj). */
+int lgu_frame_distance_f32(const float* poses, int np, const float* disps, int nd, int ht, int wd, const float* intrinsics,
+                           const long long* ii, const long long* jj, int num, float beta, float* dist, void* stream);
+int lgu_projmap_f32(const float* poses, int np, const float* disps, int nd, int ht, int wd, const float* intrinsics,
+                    const long long* ii, const long long* jj, int num, float* coords, float* valid, void* stream);
+int lgu_depth_filter_f32(const float* poses, int np, const float* disps, int nd, int ht, int wd, const float* intrinsics,
+                         const long long* ix, const float* thresh, int num, float* counter, void* stream);
+int lgu_iproj_f32(const float* poses, int np, const float* disps, int nd, int ht, int wd, const float* intrinsics,
+                  float* points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, ba, encoder, ops, sharded  # noqa: F401
+from . import _build, _lib, ba, encoder, geom, ops, sharded  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
@@ -30,7 +30,7 @@ def install_dropins(experimental_ba=False):
 
     experimental_ba=True additionally binds `droid_backends.ba` to this build's device-side bundle adjustment
     (lgu_slam_amd.ba.ba) — a first version whose parity with the reference is unpinned (the reference BA needs Eigen
-    and cannot be built here); by default that name raises, like the other out-of-scope entries."""
+    and cannot be built here); by default that name raises, like the out-of-scope corr_index_* entries."""
     if DROPIN_DIR not in sys.path:
         sys.path.insert(0, DROPIN_DIR)
     import defCorrSample  # noqa: F401

@@ -72,6 +72,11 @@ SIGNATURES = {
     "lgu_altcorr_bwd_f32": [_vp] * 6 + [_int] * 8 + [_vp],
     "lgu_defcorr_pyramid_enc_fwd_f32": [ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp, _int, _int, _int,
                                         _int, ctypes.POINTER(_int), ctypes.POINTER(_int), _int, _int, _int, _vp],
+    # poses, np, disps, nd, ht, wd, intrinsics, ...
+    "lgu_frame_distance_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _int, ctypes.c_float, _vp, _vp],
+    "lgu_projmap_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp],
+    "lgu_depth_filter_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp],
+    "lgu_iproj_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 """`torch.ops.lgu.*`: the operator layer registered with torch.library, for callers that
 dispatch through `torch.ops` (torch.compile graphs, serialized programs) instead of importing
 the drop-in modules.  Same names, arguments and in-place side effects as `ops` /
-the reference's pybind11 entries (offersample_LGS/droid.cpp:138-147, src/droid.cpp:246-247);
+the reference's pybind11 entries (offersample_LGS/droid.cpp:138-147, src/droid.cpp:239-242,246-247);
 multi-tensor returns are Python lists exactly like the reference's std::vector<Tensor>.
 Importing this module performs the registration once.
 """
@@ -9,6 +9,7 @@ from typing import List
 
 import torch
 
+from . import geom as _geom
 from . import ops as _ops
 
 _NS = "lgu"
@@ -58,6 +59,25 @@ def _altcorr_backward(fmap1: torch.Tensor, fmap2: torch.Tensor, coords: torch.Te
     return _ops.altcorr_backward(fmap1, fmap2, coords, corr_grad, radius)
 
 
+def _frame_distance(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor, ii: torch.Tensor, jj: torch.Tensor,
+                    beta: float) -> torch.Tensor:
+    return _geom.frame_distance(poses, disps, intrinsics, ii, jj, beta)
+
+
+def _projmap(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor, ii: torch.Tensor,
+             jj: torch.Tensor) -> List[torch.Tensor]:
+    return _geom.projmap(poses, disps, intrinsics, ii, jj)
+
+
+def _depth_filter(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor, ix: torch.Tensor,
+                  thresh: torch.Tensor) -> torch.Tensor:
+    return _geom.depth_filter(poses, disps, intrinsics, ix, thresh)
+
+
+def _iproj(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor) -> torch.Tensor:
+    return _geom.iproj(poses, disps, intrinsics)
+
+
 REGISTERED = {}
 if not hasattr(torch.ops, _NS) or not hasattr(getattr(torch.ops, _NS), "defCorr_index_forward"):
     for _name, _mut, _fn in (
@@ -72,3 +92,10 @@ if not hasattr(torch.ops, _NS) or not hasattr(getattr(torch.ops, _NS), "defCorr_
         ("altcorr_backward", (), _altcorr_backward),
     ):
         REGISTERED[_name] = _define(_name, _mut, _fn)
+
+# the geometry entries of droid_backends (lgu_slam_amd.geom), kept in a table of their own
+GEOM_REGISTERED = {}
+if not hasattr(getattr(torch.ops, _NS), "frame_distance"):
+    for _name, _fn in (("frame_distance", _frame_distance), ("projmap", _projmap), ("depth_filter", _depth_filter),
+                       ("iproj", _iproj)):
+        GEOM_REGISTERED[_name] = _define(_name, (), _fn)
