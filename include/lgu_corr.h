@@ -476,6 +476,38 @@ int lgu_depth_filter_f32(const float* poses, int np, const float* disps, int nd,
 int lgu_iproj_f32(const float* poses, int np, const float* disps, int nd, int ht, int wd, const float* intrinsics,
                   float* points, void* stream);
 
+/* ---- projective_transform and the motion features (reference droid_slam/geom/projective_ops.py:18-128,
+ * factor_graph.py:210-212) -----------------------------------------------------------------------------------------
+ * Reprojection, without a Lie-group library, of every pixel of frame ii[k] into frame jj[k], per batch b.
+ * poses (B,np,7) float = t, q(xyzw), used as given (not normalised); disps (B,nd,ht,wd); intrinsics (B,ni,4) = fx, fy, cx, cy PER FRAME
+ * (back-projection reads frame ii[k]'s row, projection frame jj[k]'s); ii, jj int64 device arrays of num entries, shared
+ * by the batches.  Per pixel: X0 = ((u - cx) / fx, (v - cy) / fy, 1, disp); G_ij = G_j * G_i^-1, replaced by t =
+ * (-0.1, 0, 0), q = identity where ii == jj (the stereo baseline); X1 = (R X0[0:3] + t disp, disp); Z = X1.z, replaced
+ * by 1 where Z < 0.1f; d = 1 / Z; coords = (fx (X1.x d) + cx, fy (X1.y d) + cy[, disp d]); valid = X1.z > 0.2f (float
+ * comparisons, 0.2f itself is invalid).  Values follow a fixed fp32 order, bit for bit the float32 restatement of the
+ * tests.  An edge is valid when 0 <= ii[k], jj[k] < min(np, nd, ni); for another edge nothing is dereferenced and its
+ * coordinates, Jacobians and motion channels are NaN, valid 0.  Every output element is written (no fill needed).
+ * Launched on `stream`, no host synchronisation (graph-capturable).
+ *
+ * lgu_projective_transform_f32  coords (B,num,ht,wd,2), or 3 channels with LGU_REPROJ_DEPTH; valid (B,num,ht,wd), may
+ *   be NULL.  LGU_REPROJ_JACOBIAN also writes Ji, Jj (B,num,ht,wd,2,6) and Jz (B,num,ht,wd,2,1): Jj = Jp Ja (tangent
+ *   order translation, rotation), Ji = -(Jj Adj(G_ij)), Jz = Jp (t, 1); structural zeros of Jj are written as 0.
+ *   coords (2 channels) and Jz must be 8-byte aligned, Ji and Jj 16-byte aligned (else LGU_E_UNSUPPORTED).
+ * lgu_motion_features_f32  FactorGraph.update's motion features in one launch: coords1 (B,num,ht,wd,2) as above and
+ *   motn (B,num,4,ht,wd) = clamp((x1 - u, y1 - v, tx - x1, ty - y1), -bound, bound) with target (B,num,ht,wd,2); the
+ *   clamp keeps a NaN a NaN.  valid (B,num,ht,wd) may be NULL.  coords1 and target 8-byte aligned.
+ * Sizes: B, num, np, nd, ni, ht, wd >= 0 (B, num == 0 or an empty frame: nothing is launched), ht * wd < 2^31 / 3, known
+ * flag bits only, bound >= 0, otherwise LGU_E_BADARG; more than 65535 * 256 pixels per frame or B > 65535:
+ * LGU_E_UNSUPPORTED. */
+#define LGU_REPROJ_JACOBIAN 1
+#define LGU_REPROJ_DEPTH 2
+int lgu_projective_transform_f32(const float* poses, const float* disps, const float* intrinsics, const long long* ii,
+                                 const long long* jj, int B, int np, int nd, int ni, int ht, int wd, int num, int flags,
+                                 float* coords, float* valid, float* Ji, float* Jj, float* Jz, void* stream);
+int lgu_motion_features_f32(const float* poses, const float* disps, const float* intrinsics, const long long* ii,
+                            const long long* jj, const float* target, int B, int np, int nd, int ni, int ht, int wd, int num,
+                            float bound, float* coords1, float* motn, float* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

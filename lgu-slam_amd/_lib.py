@@ -77,6 +77,9 @@ SIGNATURES = {
     "lgu_projmap_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp],
     "lgu_depth_filter_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp],
     "lgu_iproj_f32": [_vp, _int, _vp, _int, _int, _int, _vp, _vp, _vp],
+    # poses, disps, intrinsics, ii, jj, B, np, nd, ni, ht, wd, num, ...
+    "lgu_projective_transform_f32": [_vp] * 5 + [_int] * 8 + [_vp] * 6,
+    "lgu_motion_features_f32": [_vp] * 6 + [_int] * 7 + [ctypes.c_float] + [_vp] * 4,
 }
 
 _lib = None

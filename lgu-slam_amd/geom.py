@@ -11,6 +11,9 @@ buffer).  A frame index is valid when 0 <= index < min(Np, Nd); where the refere
 result is NaN (frame_distance), NaN coordinates with channel 2 = 0 and valid = 0 (projmap), a zero row (depth_filter;
 an invalid neighbour is skipped) or NaN points (iproj, frames without a pose).
 
+`projective_transform`, `reproject` and `motion_features` (geom/projective_ops.py:98-128 and the motion features of
+FactorGraph.update, without lietorch) run on csrc/reproject.hip; see their docstrings.
+
 Kernels are enqueued on the current stream of the inputs' device, without host synchronisation (graph-capturable).
 """
 import torch
@@ -150,3 +153,110 @@ def se3_inverse(poses):
     uv = 2.0 * torch.cross(v, t, dim=-1)
     ti = -(t + qi[..., 3:] * uv + torch.cross(v, uv, dim=-1))
     return torch.cat([ti, qi], -1)
+
+
+# ---- projective_transform and the motion features (csrc/reproject.hip) ----------------------------------------------
+# The reference's geom/projective_ops.py:projective_transform (:98-128) without lietorch, and FactorGraph.update's motion
+# features (factor_graph.py:210-212, :268-270) in one launch.  Forward only: no autograd.
+
+REPROJ_JACOBIAN, REPROJ_DEPTH = 1, 2     # include/lgu_corr.h LGU_REPROJ_*
+
+
+def _pose_tensor(poses):
+    """A (B,N,7) tensor as it is, or the `.data` of a group object (a lietorch SE3)."""
+    return poses if isinstance(poses, torch.Tensor) else poses.data
+
+
+def _check_no_grad(what, *tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("%s has no autograd: its outputs would carry no gradient. Call it under torch.no_grad() or "
+                           "pass detached inputs" % what)
+
+
+def _check_batched(poses, disps, intrinsics, ii, jj):
+    if poses.dim() != 3 or poses.shape[2] != 7:
+        raise RuntimeError("poses must be (B,N,7) = t, q(xyzw), got %s" % (tuple(poses.shape),))
+    if disps.dim() != 4:
+        raise RuntimeError("disps must be (B,N,ht,wd), got %s" % (tuple(disps.shape),))
+    if intrinsics.dim() != 3 or intrinsics.shape[2] != 4:
+        raise RuntimeError("intrinsics must be (B,N,4) = fx, fy, cx, cy per frame, got %s" % (tuple(intrinsics.shape),))
+    if not poses.shape[0] == disps.shape[0] == intrinsics.shape[0]:
+        raise RuntimeError("poses, disps and intrinsics must have the same batch size, got %d, %d and %d"
+                           % (poses.shape[0], disps.shape[0], intrinsics.shape[0]))
+    return _pairs(ii, jj)
+
+
+def _sizes(poses, disps, intrinsics, num):
+    B, Nd, ht, wd = disps.shape
+    return B, poses.shape[1], Nd, intrinsics.shape[1], ht, wd, num
+
+
+def projective_transform(poses, disps, intrinsics, ii, jj, jacobian=False, return_depth=False):
+    """Map the pixels of frames ii into frames jj (geom/projective_ops.py:98-128): `(coords, valid)`, or
+    `(coords, valid, (Ji, Jj, Jz))` with `jacobian`.
+
+    poses (B,N,7) float32 = t, q(xyzw) (or an object whose `.data` is that tensor, e.g. a lietorch SE3); disps
+    (B,N,ht,wd); intrinsics (B,N,4) per frame (back-projection reads frame ii's, projection frame jj's); ii, jj int64
+    (E,).  coords (B,E,ht,wd,2), a third channel disp / Z with `return_depth`; valid (B,E,ht,wd,1) float; Ji, Jj
+    (B,E,ht,wd,2,6) in lietorch's tangent order (translation, rotation); Jz (B,E,ht,wd,2,1).  Edges with ii == jj use the
+    stereo baseline t = (-0.1, 0, 0).  An index outside [0, min of the three frame counts) gives NaN values and valid 0.
+    Quaternions are used as given (lietorch may normalise non-unit ones)."""
+    poses = _pose_tensor(poses)
+    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj")
+    num = _check_batched(poses, disps, intrinsics, ii, jj)
+    _check_no_grad("projective_transform", poses, disps, intrinsics)
+    _check_device(named)
+    B, Np, Nd, Ni, ht, wd, num = _sizes(poses, disps, intrinsics, num)
+    dev = disps.device
+    C = 3 if return_depth else 2
+    coords = torch.empty((B, num, ht, wd, C), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, num, ht, wd, 1), dtype=torch.float32, device=dev)
+    if jacobian:
+        Ji = torch.empty((B, num, ht, wd, 2, 6), dtype=torch.float32, device=dev)
+        Jj = torch.empty_like(Ji)
+        Jz = torch.empty((B, num, ht, wd, 2, 1), dtype=torch.float32, device=dev)
+    if B * num * ht * wd > 0:
+        flags = (REPROJ_JACOBIAN if jacobian else 0) | (REPROJ_DEPTH if return_depth else 0)
+        jac_ptrs = (_ptr(Ji), _ptr(Jj), _ptr(Jz)) if jacobian else (None, None, None)
+        with torch.cuda.device(dev):
+            rc = _lib.load().lgu_projective_transform_f32(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
+                                                          B, Np, Nd, Ni, ht, wd, num, flags, _ptr(coords), _ptr(valid),
+                                                          *jac_ptrs, _stream(disps))
+        _lib.check(rc, "projective_transform")
+    if jacobian:
+        return coords, valid, (Ji, Jj, Jz)
+    return coords, valid
+
+
+def reproject(poses, disps, intrinsics, ii, jj):
+    """DepthVideo.reproject (depth_video.py:140-148) on the video's buffers: poses (N,7), disps (N,ht,wd), intrinsics
+    (N,4) -> coords (1,E,ht,wd,2), valid (1,E,ht,wd,1)."""
+    poses = _pose_tensor(poses)
+    return projective_transform(poses[None], disps[None], intrinsics[None], ii, jj)
+
+
+def motion_features(poses, disps, intrinsics, ii, jj, target, clamp=64.0):
+    """The motion features of FactorGraph.update (factor_graph.py:210-212) in one launch: `(coords1, motn)` with
+    coords1 = projective_transform(...)[0] (B,E,ht,wd,2) and motn (B,E,4,ht,wd) contiguous =
+    cat([coords1 - coords0, target - coords1], -1).permute(0,1,4,2,3).clamp(-clamp, clamp) (a NaN stays NaN).
+    Arguments as projective_transform's; target (B,E,ht,wd,2) float32."""
+    poses = _pose_tensor(poses)
+    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj", target, "target")
+    num = _check_batched(poses, disps, intrinsics, ii, jj)
+    B, Np, Nd, Ni, ht, wd, num = _sizes(poses, disps, intrinsics, num)
+    if tuple(target.shape) != (B, num, ht, wd, 2):
+        raise RuntimeError("target must be (B,E,ht,wd,2) = %s, got %s" % ((B, num, ht, wd, 2), tuple(target.shape)))
+    if not float(clamp) >= 0:
+        raise RuntimeError("clamp must be a non-negative bound, got %r" % (clamp,))
+    _check_no_grad("motion_features", poses, disps, intrinsics, target)
+    _check_device(named)
+    dev = disps.device
+    coords1 = torch.empty((B, num, ht, wd, 2), dtype=torch.float32, device=dev)
+    motn = torch.empty((B, num, 4, ht, wd), dtype=torch.float32, device=dev)
+    if B * num * ht * wd > 0:
+        with torch.cuda.device(dev):
+            rc = _lib.load().lgu_motion_features_f32(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
+                                                     _ptr(target), B, Np, Nd, Ni, ht, wd, num, float(clamp), _ptr(coords1),
+                                                     _ptr(motn), None, _stream(disps))
+        _lib.check(rc, "motion_features")
+    return coords1, motn

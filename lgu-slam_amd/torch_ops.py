@@ -78,6 +78,17 @@ def _iproj(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor) -
     return _geom.iproj(poses, disps, intrinsics)
 
 
+def _projective_transform(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor, ii: torch.Tensor,
+                          jj: torch.Tensor, jacobian: bool = False, return_depth: bool = False) -> List[torch.Tensor]:
+    out = _geom.projective_transform(poses, disps, intrinsics, ii, jj, jacobian=jacobian, return_depth=return_depth)
+    return [out[0], out[1]] + (list(out[2]) if jacobian else [])
+
+
+def _motion_features(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch.Tensor, ii: torch.Tensor, jj: torch.Tensor,
+                     target: torch.Tensor, clamp: float = 64.0) -> List[torch.Tensor]:
+    return list(_geom.motion_features(poses, disps, intrinsics, ii, jj, target, clamp))
+
+
 REGISTERED = {}
 if not hasattr(torch.ops, _NS) or not hasattr(getattr(torch.ops, _NS), "defCorr_index_forward"):
     for _name, _mut, _fn in (
@@ -99,3 +110,9 @@ if not hasattr(getattr(torch.ops, _NS), "frame_distance"):
     for _name, _fn in (("frame_distance", _frame_distance), ("projmap", _projmap), ("depth_filter", _depth_filter),
                        ("iproj", _iproj)):
         GEOM_REGISTERED[_name] = _define(_name, (), _fn)
+
+# projective_transform (list: coords, valid[, Ji, Jj, Jz]) and the motion features (list: coords1, motn)
+REPROJ_REGISTERED = {}
+if not hasattr(getattr(torch.ops, _NS), "projective_transform"):
+    for _name, _fn in (("projective_transform", _projective_transform), ("motion_features", _motion_features)):
+        REPROJ_REGISTERED[_name] = _define(_name, (), _fn)
