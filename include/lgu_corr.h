@@ -508,6 +508,43 @@ int lgu_motion_features_f32(const float* poses, const float* disps, const float*
                             const long long* jj, const float* target, int B, int np, int nd, int ni, int ht, int wd, int num,
                             float bound, float* coords1, float* motn, float* valid, void* stream);
 
+/* ---- GraphAgg's segment mean and the convex upsampling (reference droid_slam/droid_net.py:14-37, :53-69;
+ * depth_video.py:124-128) --------------------------------------------------------------------------------------------
+ * Launched on `stream`, no host synchronisation, no allocation (graph-capturable); no atomics: the bits do not depend on
+ * the launch geometry.
+ *
+ * lgu_scatter_mean_f32 / lgu_scatter_mean_h16  the reference's scatter_mean(src, index, dim, dim_size=M) with a 1-D index
+ *   (droid_net.py:64, GraphAgg.forward): src (outer,n,inner) float / IEEE half, index (n,) int64, out (outer,M,inner) of
+ *   src's type, FULLY written.  out[o,m,i] = S / c with S the fp32 sum of src[o,j,i] over the j with index[j] == m,
+ *   added in ascending j, c the number of those j; fp32 division, then rounded to nearest even for half.  An empty
+ *   segment gives 0.  An index outside [0, M) matches no segment (never read as an address, never counted).
+ *   16-byte loads and stores when inner is a multiple of 16 bytes and src / out are 16-byte aligned, any inner >= 1
+ *   otherwise.  outer, n, inner, M >= 0, else LGU_E_BADARG; outer * M * inner == 0 launches nothing; n == 0 writes
+ *   zeros (index may then be NULL); n > 65536, M > 65536 or outer > 65535: LGU_E_UNSUPPORTED.
+ * lgu_cvx_upsample_f32  cvx_upsample(data, mask) with data width 1 (droid_net.py:15-29): data (B,ht,wd) float, mask
+ *   (B,576,ht,wd) float or half (LGU_UPS_MASK_F16), out (B,8ht,8wd) float, FULLY written.  Mask channel k*64 + a*8 + b
+ *   weighs the neighbour (y+ky-1, x+kx-1), k = ky*3 + kx (0 outside the frame), for the output pixel (8y+a, 8x+b).  Per
+ *   output: m = max_k x_k; e_k = expf(x_k - m); s = sum e_k (ascending k); w_k = e_k / s; with LGU_UPS_HALF_WEIGHTS
+ *   (only with LGU_UPS_MASK_F16, else LGU_E_BADARG) w_k is rounded to half and back, as the softmax of a half mask
+ *   returns half weights (FactorGraph.update, autocast off); out = sum w_k * d_k, each product rounded to fp32, added
+ *   in ascending k.
+ * lgu_upsample_disps_f32  DepthVideo.upsample (depth_video.py:124-128) in one launch, in place: for u < U with
+ *   0 <= ix[u] < N, disps_up[ix[u]] (8ht,8wd) = cvx_upsample of disps[ix[u]] (ht,wd) with mask[u] (576,ht,wd).  Only
+ *   those rows of disps_up (N,8ht,8wd) are written; an ix[u] outside [0, N) writes nothing.  With duplicate entries in
+ *   ix one of the rows wins, as with index_put (the reference passes unique indices).
+ * Upsampling sizes: B, N, U, ht, wd >= 0, ht * wd <= INT_MAX / 576, known flag bits, otherwise LGU_E_BADARG; an empty
+ * frame, B, U or N == 0 launches nothing; out / disps_up must be 16-byte aligned and the mask aligned to its element,
+ * and more than 2^32 threads are LGU_E_UNSUPPORTED. */
+#define LGU_UPS_MASK_F16 1
+#define LGU_UPS_HALF_WEIGHTS 2
+int lgu_scatter_mean_f32(const float* src, const long long* index, int outer, int n, long long inner, int M, float* out,
+                         void* stream);
+int lgu_scatter_mean_h16(const void* src, const long long* index, int outer, int n, long long inner, int M, void* out,
+                         void* stream);
+int lgu_cvx_upsample_f32(const float* data, const void* mask, int B, int ht, int wd, int flags, float* out, void* stream);
+int lgu_upsample_disps_f32(const float* disps, int N, int ht, int wd, const long long* ix, int U, const void* mask,
+                           int flags, float* disps_up, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

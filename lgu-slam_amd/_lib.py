@@ -80,6 +80,13 @@ SIGNATURES = {
     # poses, disps, intrinsics, ii, jj, B, np, nd, ni, ht, wd, num, ...
     "lgu_projective_transform_f32": [_vp] * 5 + [_int] * 8 + [_vp] * 6,
     "lgu_motion_features_f32": [_vp] * 6 + [_int] * 7 + [ctypes.c_float] + [_vp] * 4,
+    # src, index, outer, n, inner, M, out, stream
+    "lgu_scatter_mean_f32": [_vp, _vp, _int, _int, ctypes.c_longlong, _int, _vp, _vp],
+    "lgu_scatter_mean_h16": [_vp, _vp, _int, _int, ctypes.c_longlong, _int, _vp, _vp],
+    # data, mask, B, ht, wd, flags, out, stream
+    "lgu_cvx_upsample_f32": [_vp, _vp] + [_int] * 4 + [_vp, _vp],
+    # disps, N, ht, wd, ix, U, mask, flags, disps_up, stream
+    "lgu_upsample_disps_f32": [_vp, _int, _int, _int, _vp, _int, _vp, _int, _vp, _vp],
 }
 
 _lib = None

@@ -5,10 +5,11 @@ the reference's pybind11 entries (offersample_LGS/droid.cpp:138-147, src/droid.c
 multi-tensor returns are Python lists exactly like the reference's std::vector<Tensor>.
 Importing this module performs the registration once.
 """
-from typing import List
+from typing import List, Optional
 
 import torch
 
+from . import aggregate as _agg
 from . import geom as _geom
 from . import ops as _ops
 
@@ -89,6 +90,23 @@ def _motion_features(poses: torch.Tensor, disps: torch.Tensor, intrinsics: torch
     return list(_geom.motion_features(poses, disps, intrinsics, ii, jj, target, clamp))
 
 
+
+def _scatter_mean(src: torch.Tensor, index: torch.Tensor, dim: int = -1, dim_size: Optional[int] = None) -> torch.Tensor:
+    return _agg.scatter_mean(src, index, dim=dim, dim_size=dim_size)
+
+
+def _cvx_upsample(data: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    return _agg.cvx_upsample(data, mask)
+
+
+def _upsample_disp(disp: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    return _agg.upsample_disp(disp, mask)
+
+
+def _upsample_disps_(disps_up: torch.Tensor, disps: torch.Tensor, ix: torch.Tensor, mask: torch.Tensor) -> None:
+    _agg.upsample_disps_(disps_up, disps, ix, mask)
+
+
 REGISTERED = {}
 if not hasattr(torch.ops, _NS) or not hasattr(getattr(torch.ops, _NS), "defCorr_index_forward"):
     for _name, _mut, _fn in (
@@ -116,3 +134,10 @@ REPROJ_REGISTERED = {}
 if not hasattr(getattr(torch.ops, _NS), "projective_transform"):
     for _name, _fn in (("projective_transform", _projective_transform), ("motion_features", _motion_features)):
         REPROJ_REGISTERED[_name] = _define(_name, (), _fn)
+
+# GraphAgg's segment mean and the convex upsampling (lgu_slam_amd.aggregate); upsample_disps_ writes disps_up in place
+AGG_REGISTERED = {}
+if not hasattr(getattr(torch.ops, _NS), "scatter_mean"):
+    for _name, _mut, _fn in (("scatter_mean", (), _scatter_mean), ("cvx_upsample", (), _cvx_upsample),
+                             ("upsample_disp", (), _upsample_disp), ("upsample_disps_", ("disps_up",), _upsample_disps_)):
+        AGG_REGISTERED[_name] = _define(_name, _mut, _fn)
