@@ -380,7 +380,8 @@ int lgu_lowmem_pyramid_calls_fwd_h16(const void* fmap1_half, const void* const* 
  * The data-parallel kernels of droid_backends.ba (reference src/droid.cpp:88-107 -> src/droid_kernels.cu:1314-1434).
  * The reference's host driver copies every block to the CPU and solves with Eigen; here lgu-slam_amd/ba.py assembles
  * and solves the reduced camera system on the device and calls these for its operands.  All index arrays are int64
- * device arrays (the dtype the reference's tensors have).  PARITY UNPINNED: see oracle/ba_oracle.py.
+ * device arrays (the dtype the reference's tensors have).  Parity: the kernels are held to the reference's own kernels
+ * (tests/test_droid_kernels_vs_reference_build.py); the assembly and solve, Eigen host code there, to oracle/ba_oracle.py.
  *
  * lgu_ba_build_f32        projective_transform_kernel (:176-425): per edge e = (ii[e] -> jj[e]): reprojection residual of
  *   targets (E,2,ht,wd) with weights (E,2,ht,wd), pose / depth Jacobians; Hs (4,E,6,6) = Hii,Hij,Hji,Hjj, vs (2,E,6),

@@ -8,8 +8,9 @@ SimplicialLLT once per iteration (host round trips inside the loop); here the re
 by Cholesky on the device — every stage is a HIP kernel of csrc/ba.hip.  The only host work is the graph bookkeeping (which E blocks meet in which
 depth frame), built once per call from ii / jj exactly as the reference's schur_block / accum_cuda do on the CPU.
 
-PARITY UNPINNED (the reference needs Eigen, absent in this image): checked against oracle/ba_oracle.py, which is itself
-pinned only by self-consistency tests (tests/test_ba.py).
+Parity: the kernels are held to the reference's own kernels (tests/test_droid_kernels_vs_reference_build.py, which also
+runs a whole step against them); the assembly and solve, Eigen host code in the reference, to oracle/ba_oracle.py
+(tests/test_ba.py).
 """
 import os
 

@@ -1,10 +1,13 @@
 """CPU restatement (numpy) of the reference's dense bundle adjustment `droid_backends.ba`
 (src/droid_kernels.cu:1314-1434 `ba_cuda` and the kernels it launches).  TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED: the reference implementation needs Eigen (src/droid_kernels.cu:15-17), which is not in this image, so
-it cannot be built here, and the reference ships no fixtures for it.  This file follows the source line by line
-(citations below) and is checked by self-consistency tests only (tests/test_ba.py: Jacobians against finite
-differences, zero residual => zero update, cost decrease, recovery of perturbed poses / depths).
+The reference's host driver needs Eigen (src/droid_kernels.cu:15-20, :1117-1434), which is not in this image, but its
+kernels do not: oracle/build_ref.py builds them without the Eigen part, and
+tests/test_droid_kernels_vs_reference_build.py holds this build's kernels to them.  What stays restated here is the
+Eigen host code, SparseBlock's assembly and solve (pose_system, schur_pairs, schur_system, solve_block); that test
+composes it with the reference's kernels into one BA step.  This file follows the source line by line (citations
+below) and is also checked by self-consistency tests (tests/test_ba.py: Jacobians against finite differences, zero
+residual => zero update, cost decrease, recovery of perturbed poses / depths).
 
 Conventions (reference): poses (N,7) = [tx,ty,tz, qx,qy,qz,qw] world-to-camera; disps (N,H,W) inverse depth;
 intrinsics (4,) = fx,fy,cx,cy; targets / weights (E,2,H,W); eta (K,H,W) or broadcastable; ii, jj (E,) int64.
@@ -108,8 +111,9 @@ def projective_transform(targets, weights, poses, disps, intrinsics, ii, jj):
         ok = z >= MIN_DEPTH
         d = np.where(ok, 1.0 / np.where(ok, z, 1), 0).astype(f32)
         d2 = d * d
-        wu = np.where(ok, f32(.001) * weights[e, 0].reshape(HW), 0).astype(f32)
-        wv = np.where(ok, f32(.001) * weights[e, 1].reshape(HW), 0).astype(f32)
+        # :305-306: the double literal .001 times the weight, rounded to float
+        wu = np.where(ok, (.001 * weights[e, 0].reshape(HW).astype(np.float64)).astype(f32), 0).astype(f32)
+        wv = np.where(ok, (.001 * weights[e, 1].reshape(HW).astype(np.float64)).astype(f32), 0).astype(f32)
         ru = (targets[e, 0].reshape(HW) - (fx * d * x + cx)).astype(f32)
         rv = (targets[e, 1].reshape(HW) - (fy * d * y + cy)).astype(f32)
         zero = np.zeros_like(x)
@@ -145,6 +149,56 @@ def accum(data, ix, jx):
     return out
 
 
+def pose_system(Hs, vs, ii, jj, t0, P):
+    """SparseBlock::update_lhs / update_rhs (:1131-1173) as ba_cuda fills the pose x pose block (:1375-1383): A (6P,6P)
+    and b (6P) in float64 from Hs (4,E,6,6) and vs (2,E,6); blocks with a negative index (poses before t0) are dropped."""
+    A = np.zeros((6 * P, 6 * P)); b = np.zeros(6 * P)
+    bi = np.concatenate([ii, ii, jj, jj]) - t0
+    bj = np.concatenate([ii, jj, ii, jj]) - t0
+    blocks = np.asarray(Hs, np.float64).reshape(-1, 6, 6)
+    for n in range(len(bi)):
+        if bi[n] >= 0 and bj[n] >= 0:
+            A[6 * bi[n]:6 * bi[n] + 6, 6 * bj[n]:6 * bj[n] + 6] += blocks[n]
+    vi = np.concatenate([ii, jj]) - t0
+    vv = np.asarray(vs, np.float64).reshape(-1, 6)
+    for n in range(len(vi)):
+        if vi[n] >= 0:
+            b[6 * vi[n]:6 * vi[n] + 6] += vv[n]
+    return A, b
+
+
+def schur_pairs(jj_exp, kk_exp, t0, t1):
+    """schur_block's enumeration (:1241-1272), in its loop order: every pair of E rows (a, c) that share a depth frame k
+    and whose pose indices i = jj_exp[a] - t0, j = jj_exp[c] - t0 lie in the window.  Returns (i list, j list, idx (n,3) =
+    (a, c, k)), the operands of EEt6x6_kernel and update_lhs."""
+    P = t1 - t0
+    graph = [[] for _ in range(P)]; index = [[] for _ in range(P)]
+    for n in range(len(jj_exp)):
+        j = int(jj_exp[n])
+        if t0 <= j <= t1 and j - t0 < P:                                               # :1248 (sic: <= t1)
+            graph[j - t0].append(int(kk_exp[n])); index[j - t0].append(n)
+    il, jl, idx = [], [], []
+    for i in range(P):
+        for j in range(P):
+            for k in range(len(graph[i])):
+                for l in range(len(graph[j])):
+                    if graph[i][k] == graph[j][l]:
+                        il.append(i); jl.append(j); idx.append((index[i][k], index[j][l], graph[i][k]))
+    return np.array(il, np.int64), np.array(jl, np.int64), np.array(idx, np.int64).reshape(-1, 3)
+
+
+def schur_system(S, v, il, jl, vrow, P):
+    """update_lhs(S, i list, j list) and update_rhs(v, jj_exp - t0) of schur_block (:1305-1308), float64."""
+    A = np.zeros((6 * P, 6 * P)); b = np.zeros(6 * P)
+    S = np.asarray(S, np.float64).reshape(-1, 6, 6); v = np.asarray(v, np.float64).reshape(-1, 6)
+    for n in range(len(il)):
+        A[6 * il[n]:6 * il[n] + 6, 6 * jl[n]:6 * jl[n] + 6] += S[n]
+    for n in range(len(vrow)):
+        if vrow[n] >= 0:
+            b[6 * vrow[n]:6 * vrow[n] + 6] += v[n]
+    return A, b
+
+
 def solve_block(A, b, lm, ep):
     """SparseBlock::solve (:1206-1231): (A + diag(ep + lm*diag(A))) x = b by Cholesky; zeros when not SPD."""
     L = A.copy()
@@ -169,19 +223,7 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
     dx = dz = None
     for _ in range(iterations):
         Hs, vs, Eii, Eij, Cii, wi = projective_transform(targets, weights, poses, disps, intrinsics, ii, jj)
-        A = np.zeros((6 * P, 6 * P)); b = np.zeros(6 * P)
-        # :1375-1382 (update_lhs / update_rhs skip negative block indices = poses before t0)
-        bi = np.concatenate([ii, ii, jj, jj]) - t0
-        bj = np.concatenate([ii, jj, ii, jj]) - t0
-        blocks = Hs.reshape(-1, 6, 6)
-        for n in range(4 * E):
-            if bi[n] >= 0 and bj[n] >= 0:
-                A[6 * bi[n]:6 * bi[n] + 6, 6 * bj[n]:6 * bj[n] + 6] += blocks[n]
-        vi = np.concatenate([ii, jj]) - t0
-        vv = vs.reshape(-1, 6)
-        for n in range(2 * E):
-            if vi[n] >= 0:
-                b[6 * vi[n]:6 * vi[n] + 6] += vv[n]
+        A, b = pose_system(Hs, vs, ii, jj, t0, P)                                      # :1375-1383
         if motion_only:
             dx = solve_block(A, b, lm, ep).reshape(P, 6)
         else:

@@ -1,7 +1,8 @@
 """Dense bundle adjustment (started in round 1).
 
-PARITY UNPINNED: the reference `droid_backends.ba` (src/droid_kernels.cu:1314-1434) needs Eigen and cannot be built in
-this image, and the reference ships no fixtures for it.  oracle/ba_oracle.py restates it line by line; these tests pin
+The reference's host driver of `droid_backends.ba` (src/droid_kernels.cu:1314-1434) needs Eigen and cannot be built in
+this image; its kernels are built without it and checked in tests/test_droid_kernels_vs_reference_build.py.
+oracle/ba_oracle.py restates the whole BA line by line; these tests pin
 the restatement by what any correct Gauss-Newton BA must do on a synthetic scene whose targets are exact
 reprojections: zero residual => zero update, quadratic convergence of the reprojection cost from perturbed poses and
 depths (which fails for a wrong Jacobian), motion-only mode, and the fixed-pose window [t0, t1).
