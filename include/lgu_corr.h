@@ -546,6 +546,47 @@ int lgu_cvx_upsample_f32(const float* data, const void* mask, int B, int ht, int
 int lgu_upsample_disps_f32(const float* disps, int N, int ht, int wd, const long long* ix, int U, const void* mask,
                            int flags, float* disps_up, void* stream);
 
+/* ---- KAN-bias GRU of the update operator (reference droid_slam/modules/gru_kanBias.py, modules/kan.py) ----------------
+ * Reference configuration only: 128 hidden channels, 448 = 128 + 320 channels of net_inp, three KANLinear(128, 128,
+ * grid_size=3, spline_order=3) heads (SiLU, standalone spline scaler).  _f32: float tensors (autocast off); _h16: IEEE
+ * half tensors with the reference's autocast rounding points (each intermediate the composition returns as half is
+ * rounded to half).  All tensors contiguous; launched on `stream`, no host synchronisation, no allocation, no atomics
+ * (graph-capturable; the bits of an edge depend only on that edge's data and H*W).  E, HW >= 0, else LGU_E_BADARG;
+ * E == 0 (or HW == 0 for gates / blend) launches nothing.
+ *
+ * lgu_kangru_context_*  glo[e,c] = mean_p r(r(s) * net[e,c,p]), s = sigmoid(r(W·net[e,:,p] + bias[c])) with r the
+ *   rounding to the tensor type (the bias joins the fp32 sum before its one rounding, as the library convolution adds
+ *   it): net (E,128,HW), weight (128,128), bias (128), glo (E,128).  The 1x1 convolution runs on the matrix cores with
+ *   fp32 accumulation.  partial: fp32 workspace of E * ceil(HW / LGU_KANGRU_CTX_PIXELS) * 128 floats (per-(edge, pixel
+ *   tile) sums, added in ascending tile order by a second launch and divided by HW).  HW == 0 with E > 0 is
+ *   LGU_E_BADARG; E > 65535 or a weight not 16-byte aligned: LGU_E_UNSUPPORTED.
+ * lgu_kan_heads_*  the three heads in one launch: out[h,e,:] = r(r(silu(x)·Wb[h]ᵀ) + r(B_h(x)·Ws[h]ᵀ)), x = glo[e,:]
+ *   (E,128), out (3,E,128).  grid (3,128,10) float: each head's knots per input feature (need not be uniform); B_h(x)
+ *   are the 6 cubic B-spline bases of each feature by the Cox–de Boor recursion in fp32, in the reference's operation
+ *   order (NaN propagates, x outside the knots gives zero bases).  wpack (384, 896) of the tensor type: row h*128 + o =
+ *   [base_weight[h][o,:] (128) | (spline_weight[h] * spline_scaler[h][...,None])[o].flatten() (768)], the product formed
+ *   in fp32 and then rounded; 16-byte aligned, else LGU_E_UNSUPPORTED.
+ * lgu_kangru_gates_*  z = r(sigmoid(r(cz + kz))) into z (E,128,HW), and r(r(sigmoid(r(cr + kr))) * net) IN PLACE over
+ *   channels 0..127 of net_inp (E,448,HW); cz, cr, net (E,128,HW), kz, kr (E,128) broadcast over the pixels.
+ * lgu_kangru_blend_*  out = r(r(r(1 - z) * net) + r(z * q)), q = r(tanh(r(cq + kq))): cq, z, net, out (E,128,HW), kq
+ *   (E,128).
+ * sigmoid(v) = 1 / (1 + expf(-v)), silu(v) = v / (1 + expf(-v)), tanh = tanhf, all in fp32. */
+#define LGU_KANGRU_CTX_PIXELS 256
+int lgu_kangru_context_f32(const float* net, const float* weight, const float* bias, int E, int HW, float* partial,
+                           float* glo, void* stream);
+int lgu_kangru_context_h16(const void* net, const void* weight, const void* bias, int E, int HW, float* partial, void* glo,
+                           void* stream);
+int lgu_kan_heads_f32(const float* glo, const float* grid, const float* wpack, int E, float* out, void* stream);
+int lgu_kan_heads_h16(const void* glo, const float* grid, const void* wpack, int E, void* out, void* stream);
+int lgu_kangru_gates_f32(const float* cz, const float* cr, const float* kz, const float* kr, const float* net, int E,
+                         int HW, float* z, float* net_inp, void* stream);
+int lgu_kangru_gates_h16(const void* cz, const void* cr, const void* kz, const void* kr, const void* net, int E, int HW,
+                         void* z, void* net_inp, void* stream);
+int lgu_kangru_blend_f32(const float* cq, const float* kq, const float* z, const float* net, int E, int HW, float* out,
+                         void* stream);
+int lgu_kangru_blend_h16(const void* cq, const void* kq, const void* z, const void* net, int E, int HW, void* out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

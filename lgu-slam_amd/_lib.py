@@ -87,6 +87,18 @@ SIGNATURES = {
     "lgu_cvx_upsample_f32": [_vp, _vp] + [_int] * 4 + [_vp, _vp],
     # disps, N, ht, wd, ix, U, mask, flags, disps_up, stream
     "lgu_upsample_disps_f32": [_vp, _int, _int, _int, _vp, _int, _vp, _int, _vp, _vp],
+    # KAN-bias GRU: net, weight, bias, E, HW, partial, glo, stream
+    "lgu_kangru_context_f32": [_vp] * 3 + [_int] * 2 + [_vp] * 3,
+    "lgu_kangru_context_h16": [_vp] * 3 + [_int] * 2 + [_vp] * 3,
+    # glo, grid, wpack, E, out, stream
+    "lgu_kan_heads_f32": [_vp] * 3 + [_int] + [_vp] * 2,
+    "lgu_kan_heads_h16": [_vp] * 3 + [_int] + [_vp] * 2,
+    # cz, cr, kz, kr, net, E, HW, z, net_inp, stream
+    "lgu_kangru_gates_f32": [_vp] * 5 + [_int] * 2 + [_vp] * 3,
+    "lgu_kangru_gates_h16": [_vp] * 5 + [_int] * 2 + [_vp] * 3,
+    # cq, kq, z, net, E, HW, out, stream
+    "lgu_kangru_blend_f32": [_vp] * 4 + [_int] * 2 + [_vp] * 2,
+    "lgu_kangru_blend_h16": [_vp] * 4 + [_int] * 2 + [_vp] * 2,
 }
 
 _lib = None

@@ -11,6 +11,7 @@ import torch
 
 from . import aggregate as _agg
 from . import geom as _geom
+from . import gru as _gru
 from . import ops as _ops
 
 _NS = "lgu"
@@ -107,6 +108,23 @@ def _upsample_disps_(disps_up: torch.Tensor, disps: torch.Tensor, ix: torch.Tens
     _agg.upsample_disps_(disps_up, disps, ix, mask)
 
 
+def _kangru_context(net: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    return _gru.kangru_context(net, weight, bias)
+
+
+def _kan_heads(glo: torch.Tensor, grid: torch.Tensor, wpack: torch.Tensor) -> torch.Tensor:
+    return _gru.kan_heads(glo, grid, wpack)
+
+
+def _kangru_gates_(net_inp: torch.Tensor, cz: torch.Tensor, cr: torch.Tensor, kz: torch.Tensor, kr: torch.Tensor,
+                   net: torch.Tensor) -> torch.Tensor:
+    return _gru.kangru_gates_(net_inp, cz, cr, kz, kr, net)
+
+
+def _kangru_blend(cq: torch.Tensor, kq: torch.Tensor, z: torch.Tensor, net: torch.Tensor) -> torch.Tensor:
+    return _gru.kangru_blend(cq, kq, z, net)
+
+
 REGISTERED = {}
 if not hasattr(torch.ops, _NS) or not hasattr(getattr(torch.ops, _NS), "defCorr_index_forward"):
     for _name, _mut, _fn in (
@@ -141,3 +159,10 @@ if not hasattr(getattr(torch.ops, _NS), "scatter_mean"):
     for _name, _mut, _fn in (("scatter_mean", (), _scatter_mean), ("cvx_upsample", (), _cvx_upsample),
                              ("upsample_disp", (), _upsample_disp), ("upsample_disps_", ("disps_up",), _upsample_disps_)):
         AGG_REGISTERED[_name] = _define(_name, _mut, _fn)
+
+# the KAN-bias GRU of the update operator (lgu_slam_amd.gru); kangru_gates_ writes r*net into net_inp in place
+GRU_REGISTERED = {}
+if not hasattr(getattr(torch.ops, _NS), "kangru_context"):
+    for _name, _mut, _fn in (("kangru_context", (), _kangru_context), ("kan_heads", (), _kan_heads),
+                             ("kangru_gates_", ("net_inp",), _kangru_gates_), ("kangru_blend", (), _kangru_blend)):
+        GRU_REGISTERED[_name] = _define(_name, _mut, _fn)
