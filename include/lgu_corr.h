@@ -587,6 +587,49 @@ int lgu_kangru_blend_f32(const float* cq, const float* kq, const float* z, const
 int lgu_kangru_blend_h16(const void* cq, const void* kq, const void* z, const void* net, int E, int HW, void* out,
                          void* stream);
 
+/* ---- proximity edges of the factor graph (reference droid_slam/factor_graph.py:319-383, add_proximity_factors) -------
+ * Window: rows i in [t0, t), columns j in [t1, t); dist holds one float per cell at f = (i - t0) * (t - t1) + (j - t1),
+ * n = (t - t0) * (t - t1) cells.  known_ii / known_jj (num_known int64 device entries, may be NULL when num_known == 0)
+ * are the edges the graph already has (ii, ii_bad, ii_inac in that order); any values are allowed, an edge outside the
+ * window kills the cells of its diamond that fall inside.
+ *   dead cell: i - rad < j, or d > 100, or j in [max(i - rad - 1, 0), i), or (stereo and i == j), or |di| + |dj| <=
+ *     max(min(|i - j| - 2, nms), 0) around a known or an accepted edge (i, j);
+ *   prefix: for i = t0 .. t-1: (i, i) if stereo, then (i, j), (j, i) for j = max(i - rad - 1, 0) .. i - 1;
+ *   selection: live cells with d <= thresh (d widened to double) in ascending (d, f); a live one is accepted while
+ *     len(edges) <= max_factors (the first failure ends the selection; max_factors < 0 accepts nothing), appends (i, j),
+ *     (j, i) and kills its diamond.
+ * Against the reference: equal distances are visited in ascending f (its argsort leaves the order open) and a NaN is
+ * never selected (it would accept one).  Any float orders correctly (negative values included, -0 as +0).
+ * Outputs: e_ii, e_jj (capacity int64 entries each, capacity >= lgu_proximity_capacity() = min(max(prefix,
+ * max_factors + 2), prefix + 2 n)) and count (one device int) = the number of entries written; nothing is written at or
+ * beyond count.  Launched on `stream`, no host synchronisation, no allocation (graph-capturable).
+ * Rules: 0 <= t1 <= t0 <= t, t1 <= max(t0 - rad - 1, 0), rad >= 0, nms >= 0, num_known >= 0, prefix <= 2^30, else
+ * LGU_E_BADARG; n > 2^24 or t > 2^30: LGU_E_UNSUPPORTED; n == 0 writes count = 0 only.
+ *
+ * lgu_proximity_select_small   everything in ONE launch of one workgroup, n <= LGU_PROXIMITY_SMALL_MAX (else
+ *   LGU_E_UNSUPPORTED): marking, 63-bit keys, a bitonic sort of the keys in LDS, the prefix and the greedy pass.
+ * lgu_proximity_keys           marking and key build for any n: work (lgu_proximity_work_bytes(), 4-byte aligned) becomes
+ *   the bitmap of the known edges' diamonds (bit f), keys[f] (n int64) = (m(d) << 31) | f >= 0 with m the order-preserving
+ *   32-bit image of d's bits, or INT64_MAX for a dead cell or d > thresh.  A memset and two launches.
+ * lgu_proximity_select_sorted  the prefix and the greedy pass over keys SORTED ascending as signed 64-bit integers (by any
+ *   sort), one workgroup; work as lgu_proximity_keys left it (it is modified).  The greedy pass takes 64 keys at a time, one per
+ *   lane: the lowest live lane is accepted, every lane drops its own candidate if it lies in the accepted diamond, the diamond
+ *   goes into the bitmap (in LDS up to 512 000 cells, else in work) for later windows; it ends at the first INT64_MAX.
+ *   Sequential depth: accepted edges + windows visited.
+ * lgu_proximity_prefix_len / _capacity / _work_bytes: host helpers, -1 for arguments outside the rules. */
+#define LGU_PROXIMITY_SMALL_MAX 4096
+long long lgu_proximity_prefix_len(int t, int t0, int rad, int stereo);
+long long lgu_proximity_capacity(int t, int t0, int t1, int rad, int stereo, long long max_factors);
+long long lgu_proximity_work_bytes(int t, int t0, int t1);
+int lgu_proximity_select_small(const float* dist, const long long* known_ii, const long long* known_jj, int num_known, int t,
+                               int t0, int t1, int rad, int nms, double thresh, long long max_factors, int stereo,
+                               long long* e_ii, long long* e_jj, long long capacity, int* count, void* stream);
+int lgu_proximity_keys(const float* dist, const long long* known_ii, const long long* known_jj, int num_known, int t, int t0,
+                       int t1, int rad, int nms, double thresh, int stereo, long long* keys, void* work, void* stream);
+int lgu_proximity_select_sorted(const long long* sorted_keys, void* work, int t, int t0, int t1, int rad, int nms,
+                                long long max_factors, int stereo, long long* e_ii, long long* e_jj, long long capacity,
+                                int* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,14 @@ SIGNATURES = {
     # cq, kq, z, net, E, HW, out, stream
     "lgu_kangru_blend_f32": [_vp] * 4 + [_int] * 2 + [_vp] * 2,
     "lgu_kangru_blend_h16": [_vp] * 4 + [_int] * 2 + [_vp] * 2,
+    # proximity edges: dist, known_ii, known_jj, num_known, t, t0, t1, rad, nms, thresh, max_factors, stereo, e_ii, e_jj,
+    # capacity, count, stream
+    "lgu_proximity_select_small": [_vp] * 3 + [_int] * 6 + [ctypes.c_double, ctypes.c_longlong, _int, _vp, _vp,
+                                                            ctypes.c_longlong, _vp, _vp],
+    # dist, known_ii, known_jj, num_known, t, t0, t1, rad, nms, thresh, stereo, keys, work, stream
+    "lgu_proximity_keys": [_vp] * 3 + [_int] * 6 + [ctypes.c_double, _int, _vp, _vp, _vp],
+    # sorted_keys, work, t, t0, t1, rad, nms, max_factors, stereo, e_ii, e_jj, capacity, count, stream
+    "lgu_proximity_select_sorted": [_vp] * 2 + [_int] * 5 + [ctypes.c_longlong, _int, _vp, _vp, ctypes.c_longlong, _vp, _vp],
 }
 
 _lib = None
@@ -143,6 +151,10 @@ def load():
     lib.lgu_ba_solve_blocked_work_doubles.argtypes = [_int]
     lib.lgu_offsets_finalize_scratch_bytes.restype = ctypes.c_longlong
     lib.lgu_offsets_finalize_scratch_bytes.argtypes = [_int]
+    for name, argtypes in (("lgu_proximity_prefix_len", [_int] * 4), ("lgu_proximity_capacity", [_int] * 5 + [ctypes.c_longlong]),
+                           ("lgu_proximity_work_bytes", [_int] * 3)):
+        getattr(lib, name).restype = ctypes.c_longlong
+        getattr(lib, name).argtypes = argtypes
     lib.lgu_version.restype = ctypes.c_char_p
     lib.lgu_debug_knobs_enabled.restype = _int
     lib.lgu_debug_knobs_enabled.argtypes = []
