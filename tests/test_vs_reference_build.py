@@ -54,14 +54,20 @@ def close(a, b, tol=1e-5):
 
 
 @pytest.mark.parametrize("shape", [(2, 12, 16, 12, 16, 3, 3.0, 1.0), (2, 48, 64, 24, 32, 3, 3.0, 0.5), (1, 30, 40, 30, 40, 3, 12.0, 1.0),
-                                   (2, 24, 32, 12, 16, 1, 3.0, 0.5)])
+                                   (2, 24, 32, 12, 16, 1, 3.0, 0.5),
+                                   # large_box (offsets 20*tanh: global-atomics branch of the backward), radius4 (two
+                                   # passes of the wave) and level1 of tests/test_backward.py
+                                   (1, 5, 7, 40, 48, 3, 3.0, 1.0, 20.0, 16.0), (1, 5, 7, 9, 11, 4, 2.0, 1.0, 3.0),
+                                   (2, 12, 16, 6, 8, 3, 3.0, 0.5)])
 def test_volume_samplers_forward_backward(lgu, ref, shape):
-    E, H1, W1, H2, W2, r, sigma, cs = shape
+    E, H1, W1, H2, W2, r, sigma, cs = shape[:8]
+    osc = shape[8] if len(shape) > 8 else 4.0
+    shift = shape[9] if len(shape) > 9 else 0.0
     rng = np.random.default_rng(1000 + H2 + r)
     rd = 2 * r + 1
     v = dev(rng.standard_normal((E, H1, W1, H2, W2)).astype(np.float32))
-    c = dev((inputs.grid_coords(rng, E, H1, W1, sigma) * cs).astype(np.float32))
-    off = (4 * np.tanh(rng.standard_normal((E, H1, W1, rd, rd, 2)))).astype(np.float32)
+    c = dev((inputs.grid_coords(rng, E, H1, W1, sigma) * cs + shift).astype(np.float32))
+    off = (osc * np.tanh(rng.standard_normal((E, H1, W1, rd, rd, 2)))).astype(np.float32)
     g = dev(rng.standard_normal((E, rd, rd, H1, W1)).astype(np.float32))
     o_r, o_m = dev(off), dev(off)
     a, = ref.defCorr_index_forward(v, c, o_r, r)
@@ -132,8 +138,12 @@ def test_lowmem_vs_reference(lgu, ref, cfg):
     assert close(b, a) and torch.equal(o_r, o_m)
 
 
-@pytest.mark.parametrize("cfg", [(3, 1, 60, 80, 30, 40, 128, 1, 3.0, 0.5), (1, 2, 8, 16, 8, 16, 64, 3, 4.0, 1.0)])
+@pytest.mark.parametrize("cfg", [(3, 1, 60, 80, 30, 40, 128, 1, 3.0, 0.5), (1, 2, 8, 16, 8, 16, 64, 3, 4.0, 1.0),
+                                 (2, 2, 8, 8, 6, 8, 32, 3, 3.0, 1.0), (2, 2, 8, 8, 6, 8, 256, 3, 3.0, 1.0)])
 def test_altcorr_vs_reference(lgu, refalt, cfg):
+    # H1 % 4 == 0 and W1 % 8 == 0 in every case: the reference's backward kernel loads coords[b][n][h1][w1] for all 4 x 8
+    # threads of a block without a bounds test (altcorr_kernel.cu:208-209), so a ragged source grid makes the REFERENCE
+    # read past the end of coords.  This project's kernel at ragged sizes is covered by tests/test_backward.py.
     B, S, H1, W1, H2, W2, C, r, sigma, cs = cfg
     case = inputs.fmap_case(4000 + H2, B, S, H1, W1, H2, W2, C, r, sigma, cs)
     f1, f2, c = dev(case["fmap1"]), dev(case["fmap2"]), dev(case["coords"])
@@ -184,6 +194,44 @@ def test_non_finite_and_wild_coordinates_match_reference(lgu, ref):
     b, = lgu.ops.lowMem_defSample(dev(fc["fmap1"]), dev(fc["fmap2"]), dev(cc), dev(fc["offset"]), 3)
     assert torch.equal(torch.isnan(a), torch.isnan(b))
     assert torch.allclose(a, b, rtol=0, atol=1e-5, equal_nan=True)
+
+
+def test_non_finite_and_wild_coordinates_backward_matches_reference(lgu, ref):
+    """The coordinate set of test_non_finite_and_wild_coordinates_match_reference (NaN, +-inf, +-3e9, a subnormal)
+    through the sampler backward, with offsets and plain: same NaN pattern and same finite values of volume_grad
+    and offset_grad as the reference's kernels.
+
+    No index either kernel forms for these inputs lies outside the slice.  Both convert floor(position) to int; on
+    this device that conversion saturates (+inf, 3e9 -> INT_MAX; -inf, -3e9 -> INT_MIN) and turns NaN into 0.  The tap
+    index is x1 = that int - r + i with 0 <= i <= 2r.  From INT_MAX it is either still >= INT_MAX - r, far above
+    W2, or has wrapped to a negative number; from INT_MIN it is negative or has wrapped to a number far above W2;
+    every one of them fails 0 <= x1 < W2, and neither kernel touches memory for a tap that fails it (the reference:
+    `if (within_bounds(y1, x1, h2, w2))` around every access; here: `valid` gates the loads, the LDS box extents,
+    both scatter branches, and the offset_grad value, which is then the 0 the reference's zero-fill leaves).  From
+    NaN, x1 lies in [-r, r]: taps with x1 < 0 are rejected as above, the others address the slice itself, and the
+    second corner x1 + 1 is used only if x1 + 1 < W2.  What NaN and inf change is the fraction dx (NaN), hence the
+    values written, never the addresses.  The same holds for y.  The finite rows are ordinary inputs."""
+    case = inputs.pyramid_case(555, 1, 16, 32, 2, 3, 3.0, 4.0, True)
+    c = case["coords"].copy()
+    c[0, 0, 0, :8] = np.nan
+    c[0, 1, 1, :8] = np.inf
+    c[0, 0, 2, :8] = -np.inf
+    c[0, :, 3, :8] = 3.0e9
+    c[0, :, 4, :8] = -3.0e9
+    c[0, 0, 5, :8] = 1e-40  # subnormal
+    g = dev(np.random.default_rng(78).standard_normal((1, 7, 7, 16, 32)).astype(np.float32))
+    for l in range(2):
+        v, cl = dev(case["volumes"][l]), (dev(c) / 2 ** l).contiguous()
+        o_r, o_m = dev(case["offsets"][l]), dev(case["offsets"][l])
+        want = ref.defCorr_index_backward(v, cl, o_r, g, 3) + ref.corr_index_backward(v, cl, g, 3)
+        got = lgu.ops.defCorr_index_backward(v, cl, o_m, g, 3) + lgu.ops.corr_index_backward(v, cl, g, 3)
+        assert torch.equal(o_r, o_m), l
+        for k, (a, b) in enumerate(zip(want, got)):
+            b = b.view(a.shape)
+            assert bool(torch.isnan(a).any()), (l, k)     # the non-finite inputs do reach every output
+            assert torch.equal(torch.isnan(a), torch.isnan(b)), (l, k)
+            fin = ~torch.isnan(a)
+            assert close(b[fin], a[fin]), (l, k)
 
 
 def test_half_feature_maps_and_fused_levels_vs_reference_call_sequence(lgu, ref, refalt):
