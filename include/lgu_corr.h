@@ -630,6 +630,35 @@ int lgu_proximity_select_sorted(const long long* sorted_keys, void* work, int t,
                                 long long max_factors, int stereo, long long* e_ii, long long* e_jj, long long capacity,
                                 int* count, void* stream);
 
+/* ---- Lie groups: the SO3 / SE3 operations of lgu_slam_amd.lie (csrc/liegroup.hip) ---------------------------------------
+ * float32, contiguous tensors.  group = LGU_LIE_SO3: an element is q = (x, y, z, w), 4 floats, tangent phi (3);
+ * LGU_LIE_SE3: (t, q), 7 floats, tangent (tau, phi) (6), translation first.  Quaternions are used as given (not
+ * normalised, not sign-flipped).  R(q) X = X + w (2 v x X) + v x (2 v x X); G H = (t_G + R_G t_H, q_G q_H) with the
+ * Hamilton product; matrix = [[R, t], [0, 1]] row-major (16 floats).  exp(tau, phi) = (V tau, [sin(th/2) phi / th,
+ * cos(th/2)]) equals the matrix exponential of [[ [phi]x, tau ], [0, 0]]; log is its inverse with |phi| <= pi (q and -q
+ * give the same result); both use series at small angles, are finite at every angle, and exp(0) / log(identity) are
+ * exact.  retr(G, a) = exp(a) G with the bits of exp followed by mul.
+ * Per element (inv, mul, retr, exp, log, matrix): n elements, one thread each, ONE launch on `stream`; n == 0 launches
+ * nothing; n < 0, an unknown group or a null pointer: LGU_E_BADARG; matrix needs a 16-byte aligned out.
+ * Broadcast (act, adj): `rows` operand rows, row r uses group element r / g_div of the COMPACT tensor G (ng elements; an
+ * expanded copy is never read).  act: width 3 rows p -> R p + t, width 4 rows (X, Y, Z, W) -> (R XYZ + t W, W).  adj:
+ * rows of the tangent size, a -> Adj(G) a, or Adj(G)^T a with transpose = 1; SE3: Adj = [[R, [t]x R], [0, R]], SO3:
+ * Adj = R.  16-byte global accesses when the operand and out are 16-byte aligned, any 4-byte alignment otherwise.  out
+ * must not overlap the inputs.  rows == 0 launches nothing; rows, ng < 0, g_div < 1, (rows - 1) / g_div >= ng, another
+ * width / transpose: LGU_E_BADARG; more than INT_MAX workgroups: LGU_E_UNSUPPORTED. */
+#define LGU_LIE_SO3 0
+#define LGU_LIE_SE3 1
+int lgu_lie_inv_f32(int group, const float* G, int n, float* out, void* stream);
+int lgu_lie_mul_f32(int group, const float* G, const float* H, int n, float* out, void* stream);
+int lgu_lie_retr_f32(int group, const float* G, const float* a, int n, float* out, void* stream);
+int lgu_lie_exp_f32(int group, const float* a, int n, float* out, void* stream);
+int lgu_lie_log_f32(int group, const float* G, int n, float* out, void* stream);
+int lgu_lie_matrix_f32(int group, const float* G, int n, float* out, void* stream);
+int lgu_lie_act_f32(int group, const float* G, long long ng, const float* p, int width, long long rows, long long g_div,
+                    float* out, void* stream);
+int lgu_lie_adj_f32(int group, const float* G, long long ng, const float* a, int transpose, long long rows,
+                    long long g_div, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

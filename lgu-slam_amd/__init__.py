@@ -1,7 +1,8 @@
 """lgu_slam_amd — MI355X (gfx950) implementation of LGU-SLAM's deformable
 correlation-sampling hot path: hand-written HIP kernels behind a C ABI
-(include/lgu_corr.h), the reference's operator signatures (`ops`), and host-side
-counterparts of its correlation glue (`corr`, `gaussian_mask`).
+(include/lgu_corr.h), the reference's operator signatures (`ops`), host-side
+counterparts of its correlation glue (`corr`, `gaussian_mask`), and the SO3 / SE3 / Sim3
+group objects its orchestration modules take from lietorch (`lie`).
 
 The on-disk directory is `lgu-slam_amd/`; `import lgu_slam_amd` works through the alias
 module `lgu_slam_amd.py` at the repository root.
@@ -9,16 +10,17 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, encoder, geom, graph, gru, ops, sharded  # noqa: F401
+from . import _build, _lib, aggregate, ba, encoder, geom, graph, gru, lie, ops, sharded  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
 from .gru import KanBiasGRU  # noqa: F401
 
-__version__ = "0.7.0"
+__version__ = "0.8.0"
 
 DROPIN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
 DROPIN_SCATTER_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin_scatter")
+DROPIN_LIETORCH_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin_lietorch")
 
 
 def build(force=False, verbose=False):
@@ -26,9 +28,10 @@ def build(force=False, verbose=False):
     return _build.build(force=force, verbose=verbose)
 
 
-def install_dropins(experimental_ba=False, torch_scatter=False):
-    """Make `import defCorrSample` / `import droid_backends` resolve to this library, so the
-    reference's droid_slam package runs on it unmodified.
+def install_dropins(experimental_ba=False, torch_scatter=False, lietorch=False):
+    """Make `import defCorrSample` / `import droid_backends` resolve to this library.  With lietorch=True and
+    torch_scatter=True the modules of the reference's droid_slam package import unmodified; `cv2` and `open3d` remain
+    the caller's.
 
     experimental_ba=True additionally binds `droid_backends.ba` to this build's device-side bundle adjustment
     (lgu_slam_amd.ba.ba) — a first version whose parity with the reference is unpinned (the reference BA needs Eigen
@@ -36,7 +39,11 @@ def install_dropins(experimental_ba=False, torch_scatter=False):
 
     torch_scatter=True also makes `import torch_scatter` resolve to dropin_scatter/torch_scatter.py (scatter_mean of
     lgu_slam_amd.aggregate; scatter_sum raises), so droid_slam/droid_net.py imports without torch_scatter.  It raises
-    if another torch_scatter is already imported.  The default leaves a real torch_scatter alone."""
+    if another torch_scatter is already imported.  The default leaves a real torch_scatter alone.
+
+    lietorch=True also makes `import lietorch` resolve to dropin_lietorch/lietorch.py (SO3, SE3, Sim3, cat and stack of
+    lgu_slam_amd.lie).  It raises if another lietorch is already imported or if the import resolves elsewhere.  The
+    default leaves a real lietorch alone."""
     if DROPIN_DIR not in sys.path:
         sys.path.insert(0, DROPIN_DIR)
     import defCorrSample  # noqa: F401
@@ -44,21 +51,22 @@ def install_dropins(experimental_ba=False, torch_scatter=False):
     if experimental_ba:
         sys.modules["droid_backends"].ba = ba.ba
     if torch_scatter:
-        _install_torch_scatter()
+        _install_module("torch_scatter", DROPIN_SCATTER_DIR)
+    if lietorch:
+        _install_module("lietorch", DROPIN_LIETORCH_DIR)
     return sys.modules["defCorrSample"], sys.modules["droid_backends"]
 
 
-def _install_torch_scatter():
-    mine = os.path.join(DROPIN_SCATTER_DIR, "torch_scatter.py")
-    have = sys.modules.get("torch_scatter")
+def _install_module(name, directory):
+    mine = os.path.join(directory, name + ".py")
+    have = sys.modules.get(name)
     if have is not None:
         if os.path.abspath(getattr(have, "__file__", "") or "") != mine:
-            raise RuntimeError("install_dropins(torch_scatter=True): another torch_scatter is already imported (%s)"
-                               % getattr(have, "__file__", have))
+            raise RuntimeError("install_dropins(%s=True): another %s is already imported (%s)"
+                               % (name, name, getattr(have, "__file__", have)))
         return
-    if DROPIN_SCATTER_DIR not in sys.path:
-        sys.path.insert(0, DROPIN_SCATTER_DIR)
-    import torch_scatter  # noqa: F401
-    if os.path.abspath(sys.modules["torch_scatter"].__file__) != mine:
-        raise RuntimeError("install_dropins(torch_scatter=True): `import torch_scatter` resolved to %s"
-                           % sys.modules["torch_scatter"].__file__)
+    if directory not in sys.path:
+        sys.path.insert(0, directory)
+    __import__(name)
+    if os.path.abspath(sys.modules[name].__file__) != mine:
+        raise RuntimeError("install_dropins(%s=True): `import %s` resolved to %s" % (name, name, sys.modules[name].__file__))

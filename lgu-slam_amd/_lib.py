@@ -107,6 +107,16 @@ SIGNATURES = {
     "lgu_proximity_keys": [_vp] * 3 + [_int] * 6 + [ctypes.c_double, _int, _vp, _vp, _vp],
     # sorted_keys, work, t, t0, t1, rad, nms, max_factors, stereo, e_ii, e_jj, capacity, count, stream
     "lgu_proximity_select_sorted": [_vp] * 2 + [_int] * 5 + [ctypes.c_longlong, _int, _vp, _vp, ctypes.c_longlong, _vp, _vp],
+    # Lie groups (group = LGU_LIE_SO3 / LGU_LIE_SE3).  Per element: group, inputs, n, out, stream
+    "lgu_lie_inv_f32": [_int, _vp, _int, _vp, _vp],
+    "lgu_lie_mul_f32": [_int, _vp, _vp, _int, _vp, _vp],
+    "lgu_lie_retr_f32": [_int, _vp, _vp, _int, _vp, _vp],
+    "lgu_lie_exp_f32": [_int, _vp, _int, _vp, _vp],
+    "lgu_lie_log_f32": [_int, _vp, _int, _vp, _vp],
+    "lgu_lie_matrix_f32": [_int, _vp, _int, _vp, _vp],
+    # broadcast: group, G, ng, operand, width | transpose, rows, g_div, out, stream
+    "lgu_lie_act_f32": [_int, _vp, ctypes.c_longlong, _vp, _int, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
+    "lgu_lie_adj_f32": [_int, _vp, ctypes.c_longlong, _vp, _int, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
 }
 
 _lib = None

@@ -24,7 +24,7 @@ extern "C" {
 // "lgu_corr <version> gfx950", followed by the extra compiler flags in brackets when the library is not the default
 // build (lgu-slam_amd/_build.py, LGU_EXTRA_HIPCC_FLAGS — experiments only): evidence records which build produced it.
 const char* lgu_version(void) {
-  return sizeof(LGU_BUILD_FLAGS) > 1 ? "lgu_corr 0.7.0 gfx950 [" LGU_BUILD_FLAGS "]" : "lgu_corr 0.7.0 gfx950";
+  return sizeof(LGU_BUILD_FLAGS) > 1 ? "lgu_corr 0.8.0 gfx950 [" LGU_BUILD_FLAGS "]" : "lgu_corr 0.8.0 gfx950";
 }
 
 int lgu_debug_knobs_enabled(void) { return lgu::g_debug_knobs ? 1 : 0; }
