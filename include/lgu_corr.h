@@ -659,6 +659,46 @@ int lgu_lie_act_f32(int group, const float* G, long long ng, const float* p, int
 int lgu_lie_adj_f32(int group, const float* G, long long ng, const float* a, int transpose, long long rows,
                     long long g_div, float* out, void* stream);
 
+/* ---- feature encoder: fused instance norm + ReLU + residual, and the frame normalisation (csrc/instnorm.hip) ------------
+ * Reference droid_slam/modules/extractor.py: BasicEncoder(output_dim=128, norm_fn='instance') builds its 15 norm sites as
+ * nn.InstanceNorm2d(planes) (:28-32, :131: biased variance, eps 1e-5, no affine terms, no running statistics).
+ * A plane is one (n, c) slice of a contiguous NCHW tensor, hw elements; a, b, out hold `planes` of them.
+ *   IN(x) = (x - mean) * rstd,  mean = sum(x) / hw,  rstd = 1 / sqrt(sum((x - mean)^2) / hw + eps)
+ * with the statistics in fp32 from the values as stored, the centred sum taken after the mean is final, every sum a
+ * tree of depth <= log2(hw) + 4 on the single-launch path (beyond it a thread first adds its ceil(hw / (1024 V)) vector
+ * sums in sequence, V = 16 / sizeof element; csrc/instnorm.hip), all arithmetic in fp32 and ONE rounding to the tensor
+ * type at the store (_h16: IEEE half).
+ *   mode 0  out = relu(IN(a))                  extractor.py:49-50, :188-189   (b is not read, may be NULL)
+ *   mode 1  out = relu(b + relu(IN(a)))        :50, :55 with downsample None  (b added as it is)
+ *   mode 2  out = relu(IN(b) + relu(IN(a)))    :50-55 with the 1x1 downsample branch and its norm3
+ *   mode 3  out = IN(a)                        a bare InstanceNorm2d          (b is not read, may be NULL)
+ * relu keeps a NaN.  out may be exactly a or exactly b; any other overlap is the caller's error.  No atomics: the bits
+ * of a plane depend on its own values, hw and eps only.
+ * hw <= lgu_instnorm_resident_limit(sizeof element) (6144 vectors of 16 bytes: 49152 halves, 24576 floats): ONE launch,
+ *   one workgroup per plane, the plane (both planes in mode 2) held in registers between the statistics and the store.
+ *   Operands need the alignment of one element only; the bits do not depend on the address.
+ * Otherwise: a statistics launch (one workgroup per plane) and an apply launch; the 16 * planes bytes between them come
+ *   from the stream-ordered allocator on `stream` (hipMallocAsync / hipFreeAsync), without host synchronisation.  Under
+ *   stream capture these become allocation and free nodes of the graph, which needs a runtime that supports them; the
+ *   single-launch path allocates nothing and captures as one kernel node.
+ * planes == 0 launches nothing; hw < 1, planes < 0, an unknown mode, eps < 0, a null or misaligned operand:
+ * LGU_E_BADARG; planes > INT_MAX or more than INT_MAX workgroups: LGU_E_UNSUPPORTED.
+ *
+ * lgu_image_normalize_u8  the frame upload of droid_slam/motion_filter.py:56-57 (image[:, [2,1,0]] / 255.0, sub_(MEAN),
+ *   div_(STDV)): img (n,3,hw) uint8 BGR, out (n,3,hw) float32 RGB, out[n,c,i] = (float(img[n,2-c,i]) * r255 - mean[c])
+ *   / std[c] in that order, r255 = (float)(1.0 / 255.0): on the device PyTorch divides a tensor by a Python number by
+ *   multiplying with the reciprocal, which is what the reference's `/ 255.0` therefore computes (the correctly rounded
+ *   quotient differs for 126 of the 256 byte values); the subtraction and the division by std are correctly rounded
+ *   fp32 ops.  Bit-identical to those four PyTorch ops on the device.  mean, std: 3 host floats each.  n, hw >= 0 (0
+ *   launches nothing), else LGU_E_BADARG. */
+int lgu_instnorm_relu_f32(const float* a, const float* b, float* out, long planes, long hw, float eps, int mode,
+                          void* stream);
+int lgu_instnorm_relu_h16(const void* a, const void* b, void* out, long planes, long hw, float eps, int mode,
+                          void* stream);
+long lgu_instnorm_resident_limit(int elem_bytes); /* largest hw served by the single-launch path; 0 for another size */
+int lgu_image_normalize_u8(const unsigned char* img, float* out, long n, long hw, const float mean[3], const float std[3],
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

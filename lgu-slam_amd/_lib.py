@@ -117,6 +117,12 @@ SIGNATURES = {
     # broadcast: group, G, ng, operand, width | transpose, rows, g_div, out, stream
     "lgu_lie_act_f32": [_int, _vp, ctypes.c_longlong, _vp, _int, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
     "lgu_lie_adj_f32": [_int, _vp, ctypes.c_longlong, _vp, _int, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp],
+    # feature encoder: a, b, out, planes, hw, eps, mode, stream
+    "lgu_instnorm_relu_f32": [_vp] * 3 + [ctypes.c_long] * 2 + [ctypes.c_float, _int, _vp],
+    "lgu_instnorm_relu_h16": [_vp] * 3 + [ctypes.c_long] * 2 + [ctypes.c_float, _int, _vp],
+    "lgu_instnorm_resident_limit": [_int],   # elem_bytes; returns long (set in load())
+    # img, out, n, hw, mean[3], std[3], stream
+    "lgu_image_normalize_u8": [_vp, _vp, ctypes.c_long, ctypes.c_long, _c_float_p, _c_float_p, _vp],
 }
 
 _lib = None
@@ -165,6 +171,7 @@ def load():
                            ("lgu_proximity_work_bytes", [_int] * 3)):
         getattr(lib, name).restype = ctypes.c_longlong
         getattr(lib, name).argtypes = argtypes
+    lib.lgu_instnorm_resident_limit.restype = ctypes.c_long
     lib.lgu_version.restype = ctypes.c_char_p
     lib.lgu_debug_knobs_enabled.restype = _int
     lib.lgu_debug_knobs_enabled.argtypes = []

@@ -1,0 +1,284 @@
+"""LGU-SLAM's feature encoder (reference droid_slam/modules/extractor.py: BasicEncoder(output_dim=128,
+norm_fn='instance'), run on every incoming frame by MotionFilter.track and PoseTrajectoryFiller) on the HIP kernels of
+csrc/instnorm.hip.
+
+The 13 convolutions stay the module's own calls (MIOpen).  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
+6 residual add + ReLU pairs, becomes one call per site group, 13 per forward: each convolution output is read once, the
+statistics are taken in fp32 from the stored values, and the block output is rounded to the tensor type once.  A call
+is one launch while H*W <= resident_limit(dtype): every site of a 384x512 frame under float16 autocast (13 launches).
+In fp32 the five 192x256 sites of such a frame exceed the limit (24576 floats) and take a statistics launch, an apply
+launch and a stream-ordered allocation each: 18 launches per forward; those calls capture in a torch.cuda.graph only if
+the runtime captures hipMallocAsync / hipFreeAsync, the single-launch calls always do.
+
+    features.install(net.fnet)                        # net.fnet(images) now reaches the fused path, state_dict unchanged
+    images = features.normalize_images(frames_u8)     # (N,3,H,W) uint8 BGR -> (1,N,3,H,W) float32, MotionFilter.track's
+    fmaps = net.fnet(images)
+
+`instance_norm_relu` and `normalize_images`: contiguous HIP device tensors only (no CPU fallback; normalize_images uploads
+a CPU uint8 image as uint8), every argument error raised before anything is launched, no host synchronisation, forward
+only: inputs that require grad are refused while grad mode is on.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .aggregate import _contiguous, _dtype_name
+from .geom import _check_device, _check_no_grad
+from .ops import _CurrentDevice, _ptr, _stream
+
+_SUFFIX = {torch.float32: "f32", torch.float16: "h16"}
+IMAGENET_MEAN = (0.485, 0.456, 0.406)     # motion_filter.py:30-31, RGB
+IMAGENET_STD = (0.229, 0.224, 0.225)
+LAYERS = ("layer1", "layer2", "layer3")
+
+
+def resident_limit(dtype):
+    """Largest H*W the single-launch kernel serves for tensors of `dtype`."""
+    return int(_lib.load().lgu_instnorm_resident_limit(torch.empty((), dtype=dtype).element_size()))
+
+
+def instance_norm_relu(a, residual=None, *, norm_residual=False, relu=True, eps=1e-5, out=None):
+    """The element-wise tail of one convolution of the encoder, fused (IN = InstanceNorm2d without affine terms or
+    running statistics, biased variance):
+
+        residual None, relu        relu(IN(a))                      extractor.py:49-50, :188-189
+        residual, not normalised   relu(residual + relu(IN(a)))     :50, :55 without a downsample branch
+        residual, norm_residual    relu(IN(residual) + relu(IN(a))) :50-55 with the 1x1 downsample branch and its norm
+        residual None, relu=False  IN(a)
+
+    a, residual, out: (N,C,H,W) float32 or float16, contiguous, same shape and dtype.  out=None allocates; out may be a
+    or residual themselves (in place), any other overlap is the caller's error.  Statistics and arithmetic are fp32, a
+    half result is rounded once."""
+    if a.dim() != 4:
+        raise RuntimeError("a must be (N,C,H,W), got %s" % (tuple(a.shape),))
+    if a.dtype not in _SUFFIX:
+        raise RuntimeError("expected scalar type Float or Half but found %s (a)" % _dtype_name(a.dtype))
+    if residual is None:
+        if norm_residual:
+            raise ValueError("norm_residual=True needs a residual")
+        mode = 0 if relu else 3
+    else:
+        if not relu:
+            raise ValueError("relu=False is served without a residual only")
+        mode = 2 if norm_residual else 1
+    named = [(a, "a")] + ([(residual, "residual")] if residual is not None else []) + ([(out, "out")] if out is not None else [])
+    for t, name in named[1:]:
+        if tuple(t.shape) != tuple(a.shape):
+            raise RuntimeError("%s must be %s, got %s" % (name, tuple(a.shape), tuple(t.shape)))
+        if t.dtype != a.dtype:
+            raise RuntimeError("expected scalar type %s but found %s (%s)" % (_dtype_name(a.dtype), _dtype_name(t.dtype), name))
+    N, C, H, W = a.shape
+    hw = H * W
+    if hw == 1:
+        raise ValueError("Expected more than 1 spatial element when training, got input size %s" % (a.size(),))
+    if not eps >= 0:
+        raise ValueError("eps must be >= 0, got %r" % (eps,))
+    _contiguous(*[x for p in named for x in p])
+    _check_no_grad("instance_norm_relu", *[t for t, _ in named])
+    _check_device(named)
+    if out is None:
+        out = torch.empty_like(a)
+    if N * C == 0:
+        return out
+    if hw == 0:
+        raise RuntimeError("instance_norm_relu: empty planes (H*W = 0), the statistics are undefined")
+    return _launch(a, residual, out, mode, float(eps))
+
+
+def _launch(a, b, out, mode, eps):
+    """The call itself, for arguments already checked (instance_norm_relu, FeatureEncoder._fused)."""
+    with _CurrentDevice(a.device):
+        rc = getattr(_lib.load(), "lgu_instnorm_relu_" + _SUFFIX[a.dtype])(
+            a.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(), a.shape[0] * a.shape[1],
+            a.shape[2] * a.shape[3], eps, mode, torch.cuda.current_stream(a.device).cuda_stream)
+    if rc:
+        _lib.check(rc, "instance_norm_relu")
+    return out
+
+
+def normalize_images(image, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """(1,N,3,H,W) float32 RGB from (N,3,H,W) uint8 BGR: channel c = (image[:, 2-c] / 255 - mean[c]) / std[c], the bits
+    of motion_filter.py:56-57 (`image[None, :, [2,1,0]].to(device) / 255.0`, `sub_(MEAN)`, `div_(STDV)`) on the device
+    (where `/ 255.0` is a product with float(1 / 255), include/lgu_corr.h) in one launch.
+    A CPU image is uploaded as uint8 to the current HIP device; mean, std: 3 numbers each, used as
+    float32."""
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise RuntimeError("image must be (N,3,H,W), got %s" % (tuple(image.shape),))
+    if image.dtype != torch.uint8:
+        raise RuntimeError("expected scalar type Byte but found %s (image)" % _dtype_name(image.dtype))
+    if len(mean) != 3 or len(std) != 3:
+        raise RuntimeError("mean and std must have 3 entries")
+    if not image.is_cuda:
+        image = image.contiguous().to(torch.device("cuda"))
+    _contiguous(image, "image")
+    N, _, H, W = image.shape
+    out = torch.empty((1, N, 3, H, W), dtype=torch.float32, device=image.device)
+    if N * H * W == 0:
+        return out
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s = (ctypes.c_float * 3)(*[float(v) for v in std])
+    with _CurrentDevice(image.device):
+        rc = _lib.load().lgu_image_normalize_u8(_ptr(image), _ptr(out), N, H * W, m, s, _stream(image))
+    _lib.check(rc, "normalize_images")
+    return out
+
+
+def _check_norm(m, channels, name):
+    if (not isinstance(m, torch.nn.InstanceNorm2d) or m.affine or m.track_running_stats
+            or getattr(m, "weight", None) is not None or getattr(m, "bias", None) is not None
+            or m.num_features != channels):
+        raise RuntimeError("FeatureEncoder: %s must be InstanceNorm2d(%d) with affine=False and track_running_stats=False"
+                           % (name, channels))
+
+
+def _check_conv(m, cin, cout, k, stride, pad, name):
+    if (not isinstance(m, torch.nn.Conv2d) or m.in_channels != cin or m.out_channels != cout or m.kernel_size != (k, k)
+            or m.stride != (stride, stride) or m.padding != (pad, pad) or m.dilation != (1, 1) or m.groups != 1
+            or m.padding_mode != "zeros"):
+        raise RuntimeError("FeatureEncoder: %s must be Conv2d(%d, %d, %d, stride=%d, padding=%d)"
+                           % (name, cin, cout, k, stride, pad))
+
+
+class FeatureEncoder:
+    """Callable stand-in for the forward of the reference's `BasicEncoder(output_dim, norm_fn='instance')`:
+
+        fused = FeatureEncoder(net.fnet)
+        fmaps = fused(images)             # = net.fnet(images), images (B,N,3,H,W)
+
+    Fused path (the module's own Conv2d calls + one csrc/instnorm.hip call per site, 13 per forward) for HIP tensors
+    when either autocast is off and the images are float32, or CUDA autocast is on with float16 (the half kernels); the
+    parameters must be float32 and contiguous NCHW, and nothing may require grad while grad mode is on.  Everything
+    else goes to the module's own forward unchanged: CPU tensors, a bfloat16 autocast, channels-last, training with
+    gradients, a dropout in training mode.
+
+    Construction refuses (RuntimeError naming the attribute) anything but conv1 / norm1 / layer1..3 of two residual
+    blocks each / conv2 with InstanceNorm2d(affine=False, track_running_stats=False) at every norm site."""
+
+    def __init__(self, module):
+        conv1 = getattr(module, "conv1", None)
+        if not isinstance(conv1, torch.nn.Conv2d):
+            raise RuntimeError("FeatureEncoder: conv1 must be a Conv2d")
+        dim = conv1.out_channels
+        _check_conv(conv1, conv1.in_channels, dim, 7, 2, 3, "conv1")
+        _check_norm(getattr(module, "norm1", None), dim, "norm1")
+        cin = dim
+        self.blocks = []
+        for name in LAYERS:
+            layer = getattr(module, name, None)
+            if not isinstance(layer, torch.nn.Sequential) or len(layer) != 2:
+                raise RuntimeError("FeatureEncoder: %s must be a Sequential of two residual blocks" % name)
+            for i, blk in enumerate(layer):
+                where = "%s.%d." % (name, i)
+                c1 = getattr(blk, "conv1", None)
+                if not isinstance(c1, torch.nn.Conv2d):
+                    raise RuntimeError("FeatureEncoder: %sconv1 must be a Conv2d" % where)
+                cout, stride = c1.out_channels, c1.stride[0]
+                _check_conv(c1, cin, cout, 3, stride, 1, where + "conv1")
+                _check_conv(getattr(blk, "conv2", None), cout, cout, 3, 1, 1, where + "conv2")
+                _check_norm(getattr(blk, "norm1", None), cout, where + "norm1")
+                _check_norm(getattr(blk, "norm2", None), cout, where + "norm2")
+                down = getattr(blk, "downsample", None)
+                if down is None:
+                    if stride != 1 or cin != cout:
+                        raise RuntimeError("FeatureEncoder: %sdownsample is missing (stride %d, %d -> %d channels)"
+                                           % (where, stride, cin, cout))
+                else:
+                    if not isinstance(down, torch.nn.Sequential) or len(down) != 2:
+                        raise RuntimeError("FeatureEncoder: %sdownsample must be Sequential(Conv2d 1x1, InstanceNorm2d)" % where)
+                    _check_conv(down[0], cin, cout, 1, stride, 0, where + "downsample.0")
+                    _check_norm(down[1], cout, where + "downsample.1")
+                    if down[1].eps != blk.norm2.eps:
+                        raise RuntimeError("FeatureEncoder: %sdownsample.1 must have norm2's eps" % where)
+                self.blocks.append(blk)
+                cin = cout
+        conv2 = getattr(module, "conv2", None)
+        if not isinstance(conv2, torch.nn.Conv2d):
+            raise RuntimeError("FeatureEncoder: conv2 must be a Conv2d")
+        _check_conv(conv2, cin, conv2.out_channels, 1, 1, 0, "conv2")
+        self.module = module
+        self.fused_calls = 0
+
+    def _convs(self):
+        m = self.module
+        convs = [m.conv1, m.conv2]
+        for blk in self.blocks:
+            convs += [blk.conv1, blk.conv2] + ([blk.downsample[0]] if blk.downsample is not None else [])
+        return convs
+
+    def _mode(self, x):
+        """torch.float16 / torch.float32 for the fused path, None for the module's forward."""
+        m = self.module
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 5 or not x.is_contiguous():
+            return None
+        if m.training and getattr(m, "dropout", None) is not None:
+            return None
+        params = [p for c in self._convs() for p in (c.weight, c.bias) if p is not None]
+        if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in params):
+            return None
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            return None
+        if torch.is_autocast_enabled("cuda"):
+            if torch.get_autocast_dtype("cuda") != torch.float16 or x.dtype not in (torch.float16, torch.float32):
+                return None
+            return torch.float16
+        return torch.float32 if x.dtype == torch.float32 else None
+
+    def _fused(self, x, dt):
+        """The fused forward, or None if a convolution returned something the kernels do not take (then nothing of the
+        caller's has been written)."""
+        m = self.module
+        b, n, c1, h1, w1 = x.shape
+
+        def ok(t):      # what instance_norm_relu would check; the shapes follow from the architecture
+            return t.dtype == dt and t.is_contiguous() and t.shape[2] * t.shape[3] > 1 and not t.requires_grad
+
+        y = m.conv1(x.view(b * n, c1, h1, w1))
+        if not ok(y):
+            return None
+        y = _launch(y, None, y, 0, m.norm1.eps)
+        for blk in self.blocks:
+            t = blk.conv1(y)
+            if not ok(t):
+                return None
+            t = blk.conv2(_launch(t, None, t, 0, blk.norm1.eps))
+            if not ok(t):
+                return None
+            if blk.downsample is None:
+                y = _launch(t, y, t, 1, blk.norm2.eps)
+            else:
+                r = blk.downsample[0](y)
+                if not ok(r):
+                    return None
+                y = _launch(t, r, t, 2, blk.norm2.eps)
+        y = m.conv2(y)
+        return y.view(b, n, y.shape[1], y.shape[2], y.shape[3])
+
+    def __call__(self, x):
+        m = self.module
+        dt = self._mode(x)
+        out = None
+        if dt is not None and x.shape[0] * x.shape[1] > 0:
+            out = self._fused(x, dt)
+        if out is None:
+            return type(m).forward(m, x)
+        self.fused_calls += 1
+        return out
+
+
+def install(module):
+    """Bind a FeatureEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
+    unchanged), so every caller of the encoder reaches the fused path.  Returns the wrapper; a second call returns the
+    one already installed."""
+    cur = module.__dict__.get("forward")
+    if isinstance(cur, FeatureEncoder):
+        return cur
+    wrapper = FeatureEncoder(module)
+    module.forward = wrapper
+    return wrapper
+
+
+def uninstall(module):
+    """Undo `install`: the class's forward is used again."""
+    if isinstance(module.__dict__.get("forward"), FeatureEncoder):
+        del module.forward
