@@ -19,6 +19,12 @@
  *     LDS on device d", the device's CU count: the same values whoever writes them) and one flag read when the library
  *     is loaded: the LGU_* debug environment variables that select superseded kernels for tests / A-B tools are
  *     honoured only if LGU_DEBUG_KNOBS=1 was set at load time — otherwise no entry point reads the environment;
+ *   - alignment: every operand must be aligned to its element, and unless the entry says otherwise that is all it
+ *     needs — the kernels then access it by element (or the host picks an element-wise kernel with the same
+ *     arithmetic) and the result does not depend on its address.  Where an entry names a stricter alignment it also
+ *     says what a contiguous operand below it gets: another kernel (and whether the bits change), LGU_E_UNSUPPORTED or
+ *     LGU_E_BADARG — every entry decides that before it launches anything.  DESIGN.md section 4.1 has the table,
+ *     operand by operand;
  *   - "fully written" outputs need no initialisation by the caller; "accumulated"
  *     outputs must be zero-filled by the caller before the call (the reference
  *     allocates them with torch::zeros / zeros_like).
@@ -54,7 +60,10 @@ const char* lgu_error_string(int code);
  * defCorrSample_kernel.cu:25-91,165-196).
  *   volume (E,H1,W1,H2,W2)  coords (E,2,H1,W1)  offset (E,H1,W1,rd,rd,2) IN/OUT
  *   corr   (E,rd,rd,H1,W1)  fully written (masked taps are written as 0).
- * Side effect kept from the reference: offset[e][y][x][r][r][0:2] = 0. */
+ * Side effect kept from the reference: offset[e][y][x][r][r][0:2] = 0.
+ * Alignment (this entry and lgu_corridx_fwd_f32): the fast kernels (radius 1..3, W2 % 4 == 0) want volume, coords and
+ * offset 16-byte aligned; otherwise the generic one-thread-per-output kernel runs, same arithmetic, same bits.  corr is
+ * stored by element. */
 int lgu_defcorr_fwd_f32(const float* volume, const float* coords, float* offset, float* corr,
                         int E, int H1, int W1, int H2, int W2, int radius, void* stream);
 
@@ -78,7 +87,8 @@ int lgu_corridx_bwd_f32(const float* volume, const float* coords, const float* c
 
 /* defCorrSample.gaussianMask            (droid.cpp:100-110, gaussianAttn.cu:19-68,134-163).
  *   means, covs (E,H1,W1,2); volume, volume1 (E,H1,W1,H2,W2); volume1 fully written
- *   (zero outside the (2*radius+1)^2 window around floor(mean)). */
+ *   (zero outside the (2*radius+1)^2 window around floor(mean)).  volume and volume1 16-byte aligned and W2 % 4 == 0:
+ *   16-byte accesses; otherwise one thread per element, same expression, same bits. */
 int lgu_gaussmask_fwd_f32(const float* means, const float* covs, const float* volume,
                           float* volume1,
                           int E, int H1, int W1, int H2, int W2, int radius, void* stream);
@@ -99,7 +109,12 @@ int lgu_gaussmask_bwd_f32(const float* means, const float* covs, const float* vo
  * flags: LGU_PYR_PROBE fuses the uncertainty probe of corr.py:94-99 as well: the 3x3
  *   plain sample of level 1 at coords/2, its unbiased variance over the 9 taps,
  *   mask = sigmoid(var), offsets[1] *= mask written back (the reference's stateful
- *   update) before level 1 is sampled. Requires L >= 2 and offsets[1] != NULL. */
+ *   update) before level 1 is sampled. Requires L >= 2 and offsets[1] != NULL.
+ * Alignment: coords, every volumes[l] and every non-null offsets[l] 16-byte aligned (and W2[l] % 4 == 0 or LGU_PYR_TILED)
+ * select the fast kernels; otherwise the generic kernel serves the plain row-major form (no flags) with the same
+ * arithmetic and bits, and every flagged form is LGU_E_UNSUPPORTED.  `out` is stored by element in the planar and the
+ * LGU_PYR_OUT_* forms.  The decision is taken for all levels before the first launch: a refused call has changed
+ * nothing. */
 #define LGU_PYR_PROBE 1
 /* LGU_PYR_TILED: volumes[l] are in this library's tiled slice layout instead of the reference's row-major
  *   H2 x W2 slices: every (edge,pixel) slice is stored as 4 x 8 element tiles (one 128-byte line each), tiles
@@ -147,7 +162,8 @@ int lgu_defcorr_pyramid_slots_fwd_f32(const float* const* volumes, const int* ed
  * edge_slot may be NULL (slot e = edge e).  flags: LGU_PYR_TILED is required; LGU_PYR_PROBE and LGU_PYR_COORDS_LAST as
  * above; the LGU_PYR_OUT_* flags do not apply (LGU_E_BADARG).  Served for radius 3, enc_n = 128, zero-offset patterns
  * the sampler handles in one launch (none / all / levels >= 2); otherwise LGU_E_UNSUPPORTED.  Offsets get the same in-place side
- * effects as in the unfused entry. */
+ * effects as in the unfused entry.  enc_w and out 16-byte, enc_b 8-byte aligned, the rest as in the unfused entry; otherwise
+ * LGU_E_UNSUPPORTED. */
 int lgu_defcorr_pyramid_enc_fwd_f32(const float* const* volumes, const int* edge_slot, const float* coords,
                                     float* const* offsets, const void* enc_w, const void* enc_b, void* out,
                                     int L, int E, int H1, int W1, const int* H2, const int* W2,
@@ -176,7 +192,8 @@ int lgu_probe_mask_scale_f32(const float* probe, float* offset, int E, int HW, i
  * 2^-22 truncation of the weights (below that convolution's own summation noise).  frames_lo (may be NULL): a second
  * half part of the input, same layout — input = frames + frames_lo — for inputs that need up to 24 bits (the residual
  * head of :219-220 takes 2 x 2 averages of the frames; split as hi = half(x), lo = half(x - hi)).  C % 32 == 0,
- * Cout <= 112; otherwise LGU_E_UNSUPPORTED. */
+ * Cout <= 112, frames, frames_lo, wpack and out 16-byte aligned (LDS-DMA of the weights, 16-byte loads of the frames, 16-byte
+ * stores); otherwise LGU_E_UNSUPPORTED. */
 int lgu_offset_conv_frames_h16(const void* frames, const void* frames_lo, const long long* ii, const long long* jj,
                                const void* wpack, const float* bias, float* out, int E, int H, int W, int C, int Cout,
                                void* stream);
@@ -192,7 +209,8 @@ int lgu_offset_conv_frames_h16(const void* frames, const void* frames_lo, const 
  *   lgu_offset_conv_worklist_h16  the partial convolutions of the worklist: wpack_a / wpack_b = the weight's two input halves
  *                                 packed like wpack above (C input channels each, C % 64 == 0), bias added to P_A only;
  *                                 PA, PB (NF, Cout, H, W) fp32; maxwork >= the worklist's possible length (sizes the grid).
- *   lgu_offset_heads_combine_f32  out[e] = PA[ii[e]] + PB[jj[e]] over rows of n floats (n % 4 == 0); *count_reset = 0. */
+ *   lgu_offset_heads_combine_f32  out[e] = PA[ii[e]] + PB[jj[e]] over rows of n floats (n % 4 == 0); *count_reset = 0.
+ * frames, frames_lo, wpack_a, wpack_b, PA, PB and out 16-byte aligned, otherwise LGU_E_UNSUPPORTED. */
 int lgu_offset_heads_mark(const long long* ii, const long long* jj, int E, int* done, int NF, int* worklist, int* count,
                           void* stream);
 int lgu_offset_conv_worklist_h16(const void* frames, const void* frames_lo, const int* worklist, const int* count, int maxwork,
@@ -209,7 +227,8 @@ int lgu_offset_heads_combine_f32(const float* PA, const float* PB, const long lo
  *   statistics per edge over (C,H,W), biased variance; both written as (E,H,W,C) fp32 — the (E,H,W,rd,rd,2) tensors
  *   the samplers take.  is_half = 1: every step is rounded to half as the framework's half kernels do; is_half = 2: the
  *   same for level 0, level 1 in fp32 — what autocast yields, which promotes the nearest upsampling to fp32.
- * scratch: lgu_offsets_finalize_scratch_bytes(E) bytes of device memory (partial sums; no initialisation needed). */
+ * scratch: lgu_offsets_finalize_scratch_bytes(E) bytes of device memory (partial sums; no initialisation needed), 8-byte
+ * aligned (it holds doubles), else LGU_E_BADARG. */
 long long lgu_offsets_finalize_scratch_bytes(int E);
 int lgu_offsets_finalize(const void* o0, const void* o1, float* out0, float* out1, void* scratch,
                          int E, int C, int H, int W, int Hl, int Wl, int is_half, float eps, void* stream);
@@ -226,7 +245,8 @@ int lgu_offsets_finalize_masked(const void* o0, const void* o1, const float* pro
  *   level l = avg_pool2d(level l-1, 2, stride 2) over the target dims, l = 1..L-1
  * levels[l] (E,H1,W1,H2>>l,W2>>l) fully written; levels[0] may alias `volume` (in place).
  * `levels` is a HOST array of L device pointers.  Requires W2 % 4 == 0 and a slice pyramid
- * that fits LDS (<= 96 KiB); otherwise LGU_E_UNSUPPORTED and the caller composes the ops. */
+ * that fits LDS (<= 96 KiB), `volume` and levels[0] 16-byte aligned (the coarser levels are stored by element); otherwise
+ * LGU_E_UNSUPPORTED and the caller composes the ops.  The same holds for the three entries below. */
 int lgu_volume_pyramid_f32(const float* means, const float* covs, const float* volume, float* const* levels, int L,
                            int E, int H1, int W1, int H2, int W2, int radius, void* stream);
 
@@ -256,8 +276,9 @@ int lgu_volume_pyramid_det(const float* means, const float* covs, const void* de
  *   fmap1, fmap2 (E, C, H, W) fp32, the reference's NCHW maps (un-scaled: the kernel applies the / 16 exactly)
  *   means, covs (E, H, W, 2), det (E*H*W) fp32 / half (det_half) or NULL: as lgu_volume_pyramid_det
  *   levels[l] (E, H, W, <tiled slice of (H >> l, W >> l)>) fp32, fully written incl. the slices' zero padding; L must be 4
- * Served: H % 8 == 0, W in {16, 32, 64}, C % 16 == 0; anything else LGU_E_UNSUPPORTED (callers take the library GEMM +
- * lgu_volume_pyramid_*).  Equal to that composition up to the GEMM's fp32 summation order. */
+ * Served: H % 8 == 0, W in {16, 32, 64}, C % 16 == 0, fmap1, fmap2 and every levels[l] 16-byte aligned; anything else
+ * LGU_E_UNSUPPORTED (callers take the library GEMM + lgu_volume_pyramid_*).  Equal to that composition up to the GEMM's
+ * fp32 summation order. */
 int lgu_volume_build_pyramid_f32(const float* fmap1, const float* fmap2, const float* means, const float* covs, const void* det,
                                  int det_half, float* const* levels, int L, int E, int C, int H, int W, int radius, void* stream);
 
@@ -268,8 +289,9 @@ int lgu_volume_build_pyramid_f32(const float* fmap1, const float* fmap2, const f
  *   CorrBlock's `t`, corr.py:57-62)
  *   workspace: E*H*W*2C halves of scratch, 16-byte aligned, distinct from feats (a first small launch re-orders the maps
  *   into MFMA fragment order there; contents afterwards unspecified)
- * Served: H % 8 == 0, W in {16, 32, 64}, C % 32 == 0.  Differs from the library half GEMM + lgu_volume_pyramid_det only where
- * a different fp32 summation order moves a sum across a half rounding boundary (one half ulp of that raw product). */
+ * Served: H % 8 == 0, W in {16, 32, 64}, C % 32 == 0, feats, workspace and every levels[l] 16-byte aligned.  Differs from
+ * the library half GEMM + lgu_volume_pyramid_det only where a different fp32 summation order moves a sum across a half
+ * rounding boundary (one half ulp of that raw product). */
 int lgu_volume_build_pyramid_h16(const void* feats, void* workspace, const float* means, const float* covs, const void* det,
                                  int det_half, float* const* levels, int L, int E, int C, int H, int W, int radius, void* stream);
 
@@ -282,7 +304,12 @@ int lgu_volume_retile_f32(const float* src, float* dst, long long nslices, int H
 /* The channel contraction of the two forward operators below runs on the matrix cores for radius 1..3 and
  * C in {16, 32, 64, 128} (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 fmaf-chain accumulation; the channel
  * summation order differs from the reference's, results agree to fp32 rounding, tests: 1e-5); other shapes take
- * VALU kernels.
+ * VALU kernels.  The matrix-core and the tile-staged kernels read the feature maps 16 bytes and coords / offset 8 bytes
+ * (one (x, y) pair) at a time: with fmap1 or fmap2 below 16-byte or coords or offset below 8-byte alignment the _f32
+ * entries (lowMem_defSample, altcorr_forward: any contiguous tensor is served) take the wave-per-pixel kernel, which
+ * accesses everything by element — another channel summation order, same 1e-5 — and the _h16 and pyramid entries, which
+ * have no such kernel, return LGU_E_UNSUPPORTED.  corr / out: 16-byte stores when it is 16-byte aligned and W1 % 4 == 0,
+ * element stores of the same values otherwise.
  *
  * defCorrSample.lowMem_defSample        (droid.cpp:124-136, lowMem_defSample.cu:27-134,137-168).
  *   fmap1 (B,H1,W1,C)  fmap2 (B,H2,W2,C)  coords (B,S,H1,W1,2) [x,y interleaved]
@@ -436,7 +463,9 @@ int lgu_ba_solve_blocked_f64(double* A, const double* b, float* x, double* work,
  * S may be NULL: motion only), written to Ad (6P x 6P row-major, double); b (6P) likewise from vs / sv.  CSR tables cover
  * all P*P (resp. P) destinations.  An entry e < 0 of sidx stands for row -e - 1 of S TRANSPOSED (S_ca = S_ac^T: the caller
  * computes the Schur products for a <= c only); direct entries first in a segment.  Per-entry arithmetic and summation
- * order are those of lgu_ba_scatter_sum_f64 (direct rows, then transposed rows). */
+ * order are those of lgu_ba_scatter_sum_f64 (direct rows, then transposed rows).
+ * Alignment: every kernel of csrc/ba.hip accesses its operands by element; lgu_ba_solve_blocked_f64 alone loads A and work
+ * 16 bytes at a time and returns LGU_E_BADARG for a misaligned one. */
 int lgu_ba_assemble_f64(const float* Hs, const long long* hptr, const long long* hidx, const float* S, const long long* sptr,
                         const long long* sidx, const float* vs, const long long* vptr, const long long* vidx, const float* sv,
                         const long long* svptr, const long long* svidx, double* Ad, double* b, int P, void* stream);
@@ -570,6 +599,8 @@ int lgu_upsample_disps_f32(const float* disps, int N, int ht, int wd, const long
  *   channels 0..127 of net_inp (E,448,HW); cz, cr, net (E,128,HW), kz, kr (E,128) broadcast over the pixels.
  * lgu_kangru_blend_*  out = r(r(r(1 - z) * net) + r(z * q)), q = r(tanh(r(cq + kq))): cq, z, net, out (E,128,HW), kq
  *   (E,128).
+ * Alignment: gates and blend go 16 bytes at a time when HW is a multiple of that and every (E,128,HW) / (E,448,HW) operand is
+ * 16-byte aligned, by element otherwise, and so does the context's load of net: same arithmetic, same bits.
  * sigmoid(v) = 1 / (1 + expf(-v)), silu(v) = v / (1 + expf(-v)), tanh = tanhf, all in fp32. */
 #define LGU_KANGRU_CTX_PIXELS 256
 int lgu_kangru_context_f32(const float* net, const float* weight, const float* bias, int E, int HW, float* partial,
@@ -616,7 +647,9 @@ int lgu_kangru_blend_h16(const void* cq, const void* kq, const void* z, const vo
  *   lane: the lowest live lane is accepted, every lane drops its own candidate if it lies in the accepted diamond, the diamond
  *   goes into the bitmap (in LDS up to 512 000 cells, else in work) for later windows; it ends at the first INT64_MAX.
  *   Sequential depth: accepted edges + windows visited.
- * lgu_proximity_prefix_len / _capacity / _work_bytes: host helpers, -1 for arguments outside the rules. */
+ * lgu_proximity_prefix_len / _capacity / _work_bytes: host helpers, -1 for arguments outside the rules.
+ * Alignment: dist, the index arrays and keys by element; work is read and or-ed as 32-bit words: 4-byte aligned, else
+ * LGU_E_BADARG. */
 #define LGU_PROXIMITY_SMALL_MAX 4096
 long long lgu_proximity_prefix_len(int t, int t0, int rad, int stereo);
 long long lgu_proximity_capacity(int t, int t0, int t1, int rad, int stereo, long long max_factors);

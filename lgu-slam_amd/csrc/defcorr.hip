@@ -916,8 +916,12 @@ static int pyramid_forward(const float* const* volumes, const float* coords, flo
   // (independent cross-check)
   const int variant = env_int("LGU_DEFCORR_VARIANT", 0);
 
-  int l0 = 0;
-  while (l0 < L) {
+  // First decide for every level group, then launch: a refusal for a later group must not leave an earlier group's
+  // side effects (centre zeroing, the probe's scaling of offsets[1]) behind.  Every LGU_E_UNSUPPORTED exit is in this loop.
+  struct Group { int l0, nl, tmpl; bool fast; };
+  Group groups[LGU_MAX_LEVELS];
+  int ngroups = 0;
+  for (int l0 = 0; l0 < L;) {
     // group up to FASTL consecutive levels into one launch; the kernel is specialised on which
     // levels of the group have null (= zero) offsets: none, all, or "levels >= 2" (CorrBlock)
     int nl = (L - l0) < FASTL ? (L - l0) : FASTL;
@@ -952,9 +956,18 @@ static int pyramid_forward(const float* const* volumes, const float* coords, flo
     if (enc && !(tiled && variant == 0 && nl == L && enc_n == ENC_N && aligned16(enc_w) && aligned16(out) &&
                  (reinterpret_cast<uintptr_t>(enc_b) & 7) == 0))
       return LGU_E_UNSUPPORTED;
+    // the generic kernel has no fused probe: the host glue then runs the probe as separate ops
+    if (!fast && pr) return LGU_E_UNSUPPORTED;
+    groups[ngroups++] = {l0, nl, tmpl, fast};
+    l0 += nl;
+  }
+
+  for (int g = 0; g < ngroups; g++) {
+    const int l0 = groups[g].l0, nl = groups[g].nl, tmpl = groups[g].tmpl;
+    const bool fast = groups[g].fast, pr = probe && l0 == 0;
     if (fast && variant == 0 && radius == 3 && L == FASTL && nl == FASTL && tmpl == 0xC && !enc && !out_nhwc) {
       const int rc = lean_pyramid_forward(volumes, coords, offsets, out, E, H1, W1, H2, W2, flags, edge_slot, st);
-      if (rc == LGU_OK) { l0 += nl; continue; }
+      if (rc == LGU_OK) continue;
       if (rc != LGU_E_UNSUPPORTED) return rc;
     }
     if (fast) {
@@ -995,8 +1008,6 @@ static int pyramid_forward(const float* const* volumes, const float* coords, flo
 #undef LGU_LAUNCH_K
       if (rc != LGU_OK) return rc;
     } else {
-      // the generic kernel has no fused probe: the host glue then runs the probe as separate ops
-      if (pr) return LGU_E_UNSUPPORTED;
       for (int l = l0; l < l0 + nl; l++) {
         const size_t total = (size_t)E * nt * H1 * W1;
         const unsigned grid = (unsigned)((total + 255) / 256 < 65535u * 16 ? (total + 255) / 256 : 65535u * 16);
@@ -1006,7 +1017,6 @@ static int pyramid_forward(const float* const* volumes, const float* coords, flo
         if (rc != LGU_OK) return rc;
       }
     }
-    l0 += nl;
   }
   return LGU_OK;
 }

@@ -327,6 +327,7 @@ int lgu_proximity_keys(const float* dist, const long long* known_ii, const long 
   if (num_known < 0) return LGU_E_BADARG;
   if (n == 0) return LGU_OK;
   if (!dist || !keys || !work || (num_known > 0 && (!known_ii || !known_jj))) return LGU_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(work) & 3) != 0) return LGU_E_BADARG;  // the bitmap is read and or-ed as 32-bit words
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const GsWin w = gs_window(t, t0, t1, rad, nms, thresh, stereo, n);
   const hipError_t e = hipMemsetAsync(work, 0, (size_t)(4 * ((n + 31) / 32)), st);
@@ -355,6 +356,7 @@ int lgu_proximity_select_sorted(const long long* sorted_keys, void* work, int t,
   const long long prefix = gs_prefix(t, t0, rad, stereo);
   if (prefix > GS_MAX_PREFIX || capacity < gs_capacity(prefix, max_factors, n)) return LGU_E_BADARG;
   if (!sorted_keys || !work || !e_ii || !e_jj) return LGU_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(work) & 3) != 0) return LGU_E_BADARG;  // 32-bit words, as lgu_proximity_keys left them
   const GsWin w = gs_window(t, t0, t1, rad, nms, 0.0, stereo, n);
   const long long words = (n + 31) / 32;
   if (words <= GS_LDS_WORDS)

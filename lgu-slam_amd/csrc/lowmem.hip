@@ -75,9 +75,14 @@ __global__ __launch_bounds__(LM_WAVES * kWave) void lowmem_kernel(const float* _
       for (int t0 = 0; t0 < nt; t0 += kWave) {
         float2 myoff = make_float2(0.f, 0.f);
         const int tl = t0 + lane;
-        if (tl < nt) {
-          if (tl == r * rd + r) *reinterpret_cast<float2*>(obase + tl * 2) = make_float2(0.f, 0.f);
-          else myoff = *reinterpret_cast<const float2*>(obase + tl * 2);
+        if (tl < nt) {  // element accesses: this kernel is the fallback for operands at any 4-byte address
+          if (tl == r * rd + r) {
+            obase[tl * 2] = 0.f;
+            obase[tl * 2 + 1] = 0.f;
+          } else {
+            myoff.x = obase[tl * 2];
+            myoff.y = obase[tl * 2 + 1];
+          }
         }
         const int tend = (nt - t0) < kWave ? (nt - t0) : kWave;
         for (int tt = 0; tt < tend; tt++) {

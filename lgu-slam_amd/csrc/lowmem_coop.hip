@@ -671,7 +671,9 @@ int lowmem_coop_dispatch(const void* fmap1, const void* const* fmap2, float* con
   if (L == 1 && !offset[0] && env_int("LGU_LOWMEM_COOP_SINGLE", 0) == 0) return -1;
   uintptr_t al = reinterpret_cast<uintptr_t>(fmap1);
   for (int l = 0; l < L; l++) al |= reinterpret_cast<uintptr_t>(fmap2[l]);
-  if ((al & 15) != 0) return -1;
+  uintptr_t al8 = reinterpret_cast<uintptr_t>(coords);  // coords and offsets (null = none) go as 8-byte (x, y) pairs
+  for (int l = 0; l < L; l++) al8 |= reinterpret_cast<uintptr_t>(offset[l]);
+  if ((al & 15) != 0 || (al8 & 7) != 0) return -1;
   if ((size_t)H1 * W1 * C >= (1u << 31) || (size_t)H1 * W1 * 49 * 8 >= (1ull << 32)) return -1;
   CoParams p = {};
   p.fmap1 = static_cast<const _Float16*>(fmap1);

@@ -594,7 +594,9 @@ static int mfma_dispatch(const MmParams& p, int C, int radius, hipStream_t st) {
   if (p.orow) return -1;  // only the cooperative kernel knows offset rows per edge
   uintptr_t al = reinterpret_cast<uintptr_t>(p.fmap1);
   for (int l = 0; l < p.L; l++) al |= reinterpret_cast<uintptr_t>(p.fmap2[l]);
-  if (radius < 1 || radius > 3 || (al & 15) != 0 || p.S > 65535) return -1;
+  uintptr_t al8 = reinterpret_cast<uintptr_t>(p.coords);  // coords and offsets (null = none) go as 8-byte (x, y) pairs
+  for (int l = 0; l < p.L; l++) al8 |= reinterpret_cast<uintptr_t>(p.offset[l]);
+  if (radius < 1 || radius > 3 || (al & 15) != 0 || (al8 & 7) != 0 || p.S > 65535) return -1;
   if ((size_t)p.H1 * p.W1 * C >= (1u << 31)) return -1;
   for (int l = 0; l < p.L; l++)
     if ((size_t)p.H2[l] * p.W2[l] * C >= (1u << 31) || p.H2[l] > 32767 || p.W2[l] > 32767) return -1;

@@ -345,7 +345,9 @@ static int launch_tile(const T* fmap1, const T* fmap2, const float* coords, floa
 template <typename T>
 static int tile_dispatch(const T* fmap1, const T* fmap2, const float* coords, float* offset, float* corr, int B, int S,
                          int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
-  const bool aligned = ((reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2)) & 15) == 0;
+  // 16-byte channel loads of the maps; coords and offset (may be null) are read and written as 8-byte (x, y) pairs
+  const bool aligned = ((reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2)) & 15) == 0 &&
+                       ((reinterpret_cast<uintptr_t>(coords) | reinterpret_cast<uintptr_t>(offset)) & 7) == 0;
   constexpr int epp = 16 / (int)sizeof(T);
   if (radius < 1 || radius > 3 || C % (2 * epp) != 0 || !aligned || S > 65535) return -1;
   if ((size_t)H2 * W2 * C >= (1u << 31) || (size_t)H1 * W1 * C >= (1u << 31)) return -1;  // 32-bit offsets inside one edge

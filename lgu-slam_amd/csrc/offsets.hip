@@ -370,6 +370,7 @@ static int offsets_finalize_impl(const void* o0, const void* o1, const float* pr
                                  int E, int C, int H, int W, int Hl, int Wl, int is_half, float eps, void* stream) {
   using namespace lgu;
   if (!o0 || !o1 || !out0 || !out1 || !scratch) return LGU_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(scratch) & 7) != 0) return LGU_E_BADARG;  // partial sums are doubles
   if (E < 0 || C < 1 || H < 1 || W < 1 || Hl < 1 || Wl < 1) return LGU_E_BADARG;
   if (E == 0) return LGU_OK;
   const size_t lds = sizeof(float) * 2 * (size_t)C * (OF_TP + 1);

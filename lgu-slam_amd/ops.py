@@ -708,6 +708,11 @@ class OffsetHeadCache:
             raise RuntimeError("OffsetHeadCache: frames must be contiguous (NF,H,W,%d)" % C)
         if (Cout * H * W) % 4 != 0:
             raise _lib.UnsupportedShape("OffsetHeadCache: Cout*H*W must be a multiple of 4")
+        # what lgu_offset_conv_worklist_h16 would refuse is refused here: its refusal would come after the mark pass
+        # had claimed the frames, and leave a cache that counts partials it never computed
+        for t, name in ((frames, "frames"), (frames_lo, "frames_lo"), (wa, "wpack_a"), (wb, "wpack_b")):
+            if t is not None and t.data_ptr() % 16 != 0:
+                raise _lib.UnsupportedShape("OffsetHeadCache: %s must be 16-byte aligned" % name)
         self.frames, self.frames_lo, self.parts = frames, frames_lo, parts
         self.NF, self.H, self.W, self.C, self.Cout = NF, H, W, C, Cout
         dev = frames.device
@@ -724,6 +729,8 @@ class OffsetHeadCache:
         _check_dtype(ii, "ii", torch.int64)
         _check_dtype(jj, "jj", torch.int64)
         E = ii.shape[0]
+        if 2 * E > 65535:   # the worklist convolution sizes its grid with 2E
+            raise _lib.UnsupportedShape("OffsetHeadCache: at most 32767 edges per call")
         if self.worklist is None or self.worklist.numel() < 2 * E:
             self.worklist = torch.empty(max(2 * E, 64), dtype=torch.int32, device=self.frames.device)
         if E:
