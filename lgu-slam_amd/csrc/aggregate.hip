@@ -34,9 +34,6 @@ constexpr int SM_MAX_N = 65536, SM_MAX_M = 65536;
 constexpr int CVX_XV = LGU_CVX_XV;
 constexpr int SM_UNROLL = 4;  // segment rows loaded before they are added (8 and 16 measured no faster)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // 16 bytes of T: four floats or eight halves.
 template <typename T> struct Vec16;

@@ -167,8 +167,6 @@ __global__ __launch_bounds__(CH_T) void chol_panel_kernel(double* A, double* ext
 // accumulators start as the tile itself and the panel enters negated, so there is no LDS, no barrier and no separate
 // read-modify-write pass.  (The 64 x 64 LDS-staged tiles this replaces took 14 us per launch, a chain of global -> LDS ->
 // barrier -> 256 LDS reads per thread -> read-modify-write; whole panels only: w == CH_NB.)
-typedef double chd4 __attribute__((ext_vector_type(4)));
-typedef double chd2 __attribute__((ext_vector_type(2)));
 constexpr int CH_UR = 16, CH_UC = 64;
 __global__ __launch_bounds__(kWave) void chol_update_kernel(double* A, double* ext, const double* __restrict__ stage, int n, int k0, int w) {
   const int lane = threadIdx.x;
@@ -185,24 +183,24 @@ __global__ __launch_bounds__(kWave) void chol_update_kernel(double* A, double* e
   {
     const int gi = i0 + li;
     // 16-byte loads: n = 6 P is even, k0 a multiple of 32, A and ext 16-byte aligned (checked by the host entry)
-    const chd2* const ar = gi <= n ? reinterpret_cast<const chd2*>(chol_row(A, ext, n, gi) + k0 + 8 * q) : nullptr;
+    const f64x2* const ar = gi <= n ? reinterpret_cast<const f64x2*>(chol_row(A, ext, n, gi) + k0 + 8 * q) : nullptr;
 #pragma unroll
     for (int s2 = 0; s2 < 4; s2++) {
-      const chd2 v = ar ? ar[s2] : chd2{0.0, 0.0};
+      const f64x2 v = ar ? ar[s2] : f64x2{0.0, 0.0};
       av[2 * s2] = -v[0]; av[2 * s2 + 1] = -v[1];
     }
   }
 #pragma unroll
   for (int jb = 0; jb < 4; jb++) {
     const int gj = j0 + 16 * jb + li;
-    const chd2* const br = gj < n ? reinterpret_cast<const chd2*>(A + (size_t)gj * n + k0 + 8 * q) : nullptr;
+    const f64x2* const br = gj < n ? reinterpret_cast<const f64x2*>(A + (size_t)gj * n + k0 + 8 * q) : nullptr;
 #pragma unroll
     for (int s2 = 0; s2 < 4; s2++) {
-      const chd2 v = br ? br[s2] : chd2{0.0, 0.0};
+      const f64x2 v = br ? br[s2] : f64x2{0.0, 0.0};
       bv[jb][2 * s2] = v[0]; bv[jb][2 * s2 + 1] = v[1];
     }
   }
-  chd4 acc[4];
+  f64x4 acc[4];
   double* cp[4];
 #pragma unroll
   for (int r = 0; r < 4; r++) {

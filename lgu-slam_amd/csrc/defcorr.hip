@@ -29,13 +29,9 @@
 //                             global_load_lds_dwordx4 into an LDS pool — same HBM bytes,
 //                             1.8x the instructions, kept for A/B              [variant 1]
 //     defcorr_generic_kernel  one thread per output: any radius / shape         [variant 2]
-#include "lgu_common.hpp"
+#include "defcorr_lean.hpp"
 
 namespace lgu {
-
-// csrc/defcorr_lean.hip: the production configuration (radius 3, 4 levels, offsets on levels 0-1, planar output)
-int lean_pyramid_forward(const float* const* volumes, const float* coords, float* const* offsets, float* out, int E,
-                         int H1, int W1, const int* H2, const int* W2, int flags, const int* edge_slot, hipStream_t st);
 
 constexpr int TP = 16;               // pixels (along x) per workgroup of the staged kernel / narrow gather tiles
 constexpr int NWAVE = 4;             // waves per workgroup
@@ -78,9 +74,6 @@ constexpr int ENC_XPITCH = 200;  // halves per pixel row of the LDS operand tile
 constexpr int ENC_MAXKS = 7;     // k-steps of 32: up to 224 input channels (4 levels x 49 taps = 196)
 constexpr int ENC_XBYTES = (32 * ENC_XPITCH + 64) * 2;             // operand tile (+ the over-read of the last row)
 constexpr int ENC_LDS_BYTES = ENC_XBYTES + 8 * ENC_MAXKS * 1024;   // + the weight fragments: 70 272 bytes, 2 workgroups per CU
-typedef _Float16 enc_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 enc_half4 __attribute__((ext_vector_type(4)));
-typedef float enc_f32x4 __attribute__((ext_vector_type(4)));
 
 // Position of target element (y, x) inside a slice.  Reference layout: row-major H2 x W2.
 // Tiled layout (LGU_PYR_TILED): 4 x 8 element tiles = one 128-byte line each, tiles row-major over the slice
@@ -454,7 +447,6 @@ __global__ __launch_bounds__(NWAVE * kWave) void defcorr_pyr_kernel(const PyrPar
 // 771 L1 accesses per wave, 0.86 per CU cycle).  A pair never leaves its line except when the tap's x is the last
 // column of a 4 x 8 tile (1 lane in 8): those lanes fetch the pair one element to the left and take the right
 // neighbours with two extra instructions that only they execute.
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 
 template <int R, bool PROBE, int ZMASK, int GP, int TPX, bool TILED, int OUTM = 0, bool PAIR = false>
 __global__ __launch_bounds__((TPX / GP) * kWave, GP == 4 ? (PROBE ? 4 : 5) : 8) void defcorr_gather_kernel(const PyrParams p) {
@@ -752,33 +744,32 @@ __global__ __launch_bounds__((TPX / GP) * kWave, GP == 4 ? (PROBE ? 4 : 5) : 8) 
     const int mt = w & 7, ntile = w >> 3;  // channel tile, pixel tile of this wave
     const int lr = lane & 15, kg = lane >> 4;
     const int nks = p.enc_kp >> 5;
-    const enc_half4 bias = *reinterpret_cast<const enc_half4*>(reinterpret_cast<const _Float16*>(p.enc_b) + mt * 16 + kg * 4);
+    const f16x4 bias = *reinterpret_cast<const f16x4*>(reinterpret_cast<const _Float16*>(p.enc_b) + mt * 16 + kg * 4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's weight DMA (the compiler does not track it)
     __syncthreads();
     const char* const wl = reinterpret_cast<const char*>(lds4) + ENC_XBYTES + mt * (ENC_MAXKS * 1024) + lane * 16;
     const _Float16* xrow = reinterpret_cast<const _Float16*>(lds4) + (ntile * 16 + lr) * ENC_XPITCH + kg * 8;
     // Entries at k >= Ctot of the last k-step are not this pixel's samples (row padding / the next row).  W1 is zero
     // there, but 0 * NaN is NaN, so they are cleared on the B side as well: one 128-bit lane mask, built once.
-    typedef unsigned enc_u32x4 __attribute__((ext_vector_type(4)));
     const int nvalid = p.Ctot - ((nks - 1) * 32 + kg * 8);  // valid entries of this lane's 8 in the last k-step
-    enc_u32x4 lastmask;
+    u32x4 lastmask;
 #pragma unroll
     for (int j = 0; j < 4; j++) lastmask[j] = nvalid >= 2 * j + 2 ? 0xffffffffu : nvalid == 2 * j + 1 ? 0x0000ffffu : 0u;
-    enc_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int ks = 0; ks < ENC_MAXKS; ks++) {
       if (ks >= nks) break;
-      const enc_half8 a = *reinterpret_cast<const enc_half8*>(wl + ks * 1024);
-      enc_half8 b = *reinterpret_cast<const enc_half8*>(xrow + ks * 32);
-      if (ks == nks - 1) b = __builtin_bit_cast(enc_half8, __builtin_bit_cast(enc_u32x4, b) & lastmask);
+      const f16x8 a = *reinterpret_cast<const f16x8*>(wl + ks * 1024);
+      f16x8 b = *reinterpret_cast<const f16x8*>(xrow + ks * 32);
+      if (ks == nks - 1) b = __builtin_bit_cast(f16x8, __builtin_bit_cast(u32x4, b) & lastmask);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
     }
     const int pxo = xbase + ntile * 16 + lr;
     if (pxo < p.W1) {
-      enc_half4 o;
+      f16x4 o;
 #pragma unroll
       for (int t = 0; t < 4; t++) o[t] = (_Float16)fmaxf(acc[t] + (float)bias[t], 0.0f);
-      *reinterpret_cast<enc_half4*>(reinterpret_cast<_Float16*>(p.out) + (row_pix + pxo) * ENC_N + mt * 16 + kg * 4) = o;
+      *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(p.out) + (row_pix + pxo) * ENC_N + mt * 16 + kg * 4) = o;
     }
     return;
   }

@@ -19,7 +19,7 @@
 // Decomposition is unchanged: workgroup = 16 x-adjacent pixels of one row (8 waves), wave = 2 pixels, lanes = taps for
 // the offset levels and lattice points for the zero-offset levels, LDS transpose tile, 64-byte row segments, tiles dealt
 // to XCDs in contiguous runs.
-#include "lgu_common.hpp"
+#include "defcorr_lean.hpp"
 
 namespace lgu {
 
@@ -34,10 +34,6 @@ struct Geo {
   int ssz[NL];          // floats per (edge, pixel) slice as stored
   int tpr[NL];          // tiled layout: 4 x 8 tiles per tile row
 };
-
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-typedef float f32x2a __attribute__((ext_vector_type(2)));
-typedef float f32x4a __attribute__((ext_vector_type(4)));
 
 // element position inside a slice, in floats (separable: fy(y) + fx(x))
 template <bool TILED>
@@ -110,11 +106,11 @@ __global__ __launch_bounds__(NWV* kWave, 6) void defcorr_lean_kernel(
   const float* ob0 = off0 + (size_t)(row_pix + pxa) * (NT * 2);
   const float* ob1 = off1 + (size_t)(row_pix + pxa) * (NT * 2);
   const unsigned dpx = (pxb - pxa) * (NT * 2 * 4);                // 392 or 0 bytes (uniform)
-  f32x2a of[GP][2];
-  of[0][0] = ldg<f32x2a>(ob0, lane_c * 8u);
-  of[1][0] = ldg<f32x2a>(ob0, lane_c * 8u + dpx);
-  of[0][1] = ldg<f32x2a>(ob1, lane_c * 8u);
-  of[1][1] = ldg<f32x2a>(ob1, lane_c * 8u + dpx);
+  f32x2 of[GP][2];
+  of[0][0] = ldg<f32x2>(ob0, lane_c * 8u);
+  of[1][0] = ldg<f32x2>(ob0, lane_c * 8u + dpx);
+  of[0][1] = ldg<f32x2>(ob1, lane_c * 8u);
+  of[1][1] = ldg<f32x2>(ob1, lane_c * 8u + dpx);
   float cx[GP], cy[GP];
   {
     const unsigned HW1 = (unsigned)H1 * W1;
@@ -139,14 +135,14 @@ __global__ __launch_bounds__(NWV* kWave, 6) void defcorr_lean_kernel(
 #pragma unroll
       for (int l = 0; l < 2; l++) nz |= __builtin_bit_cast(unsigned, of[k][l].x) | __builtin_bit_cast(unsigned, of[k][l].y);
     if (centre && nz != 0u) {   // first lookup of a volume only
-      const f32x2a z = {0.0f, 0.0f};
+      const f32x2 z = {0.0f, 0.0f};
       if (pv[0]) {
-        reinterpret_cast<f32x2a*>(off0 + (size_t)(row_pix + pxa) * (NT * 2))[R * RD + R] = z;
-        reinterpret_cast<f32x2a*>(off1 + (size_t)(row_pix + pxa) * (NT * 2))[R * RD + R] = z;
+        reinterpret_cast<f32x2*>(off0 + (size_t)(row_pix + pxa) * (NT * 2))[R * RD + R] = z;
+        reinterpret_cast<f32x2*>(off1 + (size_t)(row_pix + pxa) * (NT * 2))[R * RD + R] = z;
       }
       if (pv[1]) {
-        reinterpret_cast<f32x2a*>(off0 + (size_t)(row_pix + pxb) * (NT * 2))[R * RD + R] = z;
-        reinterpret_cast<f32x2a*>(off1 + (size_t)(row_pix + pxb) * (NT * 2))[R * RD + R] = z;
+        reinterpret_cast<f32x2*>(off0 + (size_t)(row_pix + pxb) * (NT * 2))[R * RD + R] = z;
+        reinterpret_cast<f32x2*>(off1 + (size_t)(row_pix + pxb) * (NT * 2))[R * RD + R] = z;
       }
     }
 #pragma unroll
@@ -283,7 +279,7 @@ __global__ __launch_bounds__(NWV* kWave, 6) void defcorr_lean_kernel(
       of[k][1].y *= mk[k];
       // persistent offset[1] *= mask (corr.py:99); the centre stays 0
       if (tap && !centre && pv[k])
-        reinterpret_cast<f32x2a*>(off1 + (size_t)(row_pix + (k ? pxb : pxa)) * (NT * 2))[lane] = of[k][1];
+        reinterpret_cast<f32x2*>(off1 + (size_t)(row_pix + (k ? pxb : pxa)) * (NT * 2))[lane] = of[k][1];
       issue_offset_level(k, 1);
     }
   }
@@ -358,8 +354,7 @@ static unsigned magic_u32(unsigned d) { return d == 1 ? 0u : (unsigned)((0x10000
 
 }  // namespace lean
 
-// Launcher, called by pyramid_forward (defcorr.hip) when the launch is the production configuration.  Returns
-// LGU_E_UNSUPPORTED for anything else: the caller then takes the general kernel.
+// Launcher (defcorr_lean.hpp), called by pyramid_forward (defcorr.hip).
 int lean_pyramid_forward(const float* const* volumes, const float* coords, float* const* offsets, float* out, int E,
                          int H1, int W1, const int* H2, const int* W2, int flags, const int* edge_slot, hipStream_t st) {
   using namespace lean;

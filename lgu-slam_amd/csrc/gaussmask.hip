@@ -192,9 +192,8 @@ __global__ __launch_bounds__(VP_THREADS) void volume_pyramid_kernel(const VolPyr
   }
   const int cx = (int)floorf(mx), cy = (int)floorf(my);
   const int xa = cx - p.r, xb = cx + p.r, ya = cy - p.r, yb = cy + p.r;
-  typedef _Float16 vp_half4 __attribute__((ext_vector_type(4)));
   const float4* vin = reinterpret_cast<const float4*>(static_cast<const float*>(p.vin) + (HALF_IN ? 0 : pix * (size_t)HW2));
-  const vp_half4* vinh = reinterpret_cast<const vp_half4*>(static_cast<const _Float16*>(p.vin) + (HALF_IN ? pix * (size_t)HW2 : 0));
+  const f16x4* vinh = reinterpret_cast<const f16x4*>(static_cast<const _Float16*>(p.vin) + (HALF_IN ? pix * (size_t)HW2 : 0));
   const int tpr0 = (W2 + 7) >> 3;
   const int ssz0 = TILED ? ((H2 + 3) >> 2) * tpr0 * 32 : HW2;
   float4* vout = reinterpret_cast<float4*>(p.out[0] + pix * (size_t)ssz0);
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(VP_THREADS) void volume_pyramid_kernel(const VolPyr
     const int x4 = (gi - row * g_per_row) << 2;
     float4 v;
     if constexpr (HALF_IN) {
-      const vp_half4 hv = vinh[gi];
+      const f16x4 hv = vinh[gi];
       v = make_float4((float)hv[0], (float)hv[1], (float)hv[2], (float)hv[3]);
     } else {
       v = vin[gi];

@@ -46,20 +46,17 @@ constexpr int IN_SMALL = 256, IN_BIG = 1024;
 constexpr int IN_APPLY_THREADS = 256;
 constexpr int IMG_THREADS = 256;
 
-typedef float in_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 in_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned char in_u8x4 __attribute__((ext_vector_type(4)));
 
 // 16 bytes of T; `mem` is the same vector with the alignment of one element, for accesses at any element address.
 template <typename T> struct InVec;
 template <> struct InVec<float> {
-  typedef in_f32x4 type;
-  typedef in_f32x4 mem __attribute__((aligned(4)));
+  typedef f32x4 type;
+  typedef f32x4 mem __attribute__((aligned(4)));
   static constexpr int n = 4;
 };
 template <> struct InVec<_Float16> {
-  typedef in_f16x8 type;
-  typedef in_f16x8 mem __attribute__((aligned(2)));
+  typedef f16x8 type;
+  typedef f16x8 mem __attribute__((aligned(2)));
   static constexpr int n = 8;
 };
 
@@ -71,12 +68,10 @@ __device__ __forceinline__ float six_tree(const float (&s)[IN_NV]) { return ((s[
 // The V values of a packed vector as fp32.  A plane's registers are unpacked three times (sum, centred sum, store);
 // the empty asm makes each unpacking its own computation, otherwise the compiler keeps the fp32 copies of a half plane
 // alive from the first use on (96 registers in mode 2) and spills.
-typedef unsigned in_u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 in_f16x2 __attribute__((ext_vector_type(2)));
 
 template <typename T>
 __device__ __forceinline__ void unpack(const typename InVec<T>::type& v, float (&x)[InVec<T>::n]) {
-  const in_u32x4 w4 = __builtin_bit_cast(in_u32x4, v);
+  const u32x4 w4 = __builtin_bit_cast(u32x4, v);
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     unsigned w = w4[i];
@@ -84,7 +79,7 @@ __device__ __forceinline__ void unpack(const typename InVec<T>::type& v, float (
     if constexpr (InVec<T>::n == 4) {
       x[i] = __builtin_bit_cast(float, w);
     } else {
-      const in_f16x2 h = __builtin_bit_cast(in_f16x2, w);
+      const f16x2 h = __builtin_bit_cast(f16x2, w);
       x[2 * i] = (float)h[0];
       x[2 * i + 1] = (float)h[1];
     }
@@ -413,11 +408,11 @@ __global__ __launch_bounds__(IMG_THREADS) void image_normalize_kernel(const unsi
   const size_t src = ((size_t)n * 3 + (2 - c)) * (size_t)hw + (size_t)g * XV;
   const size_t dst = (size_t)nc * (size_t)hw + (size_t)g * XV;
   if (XV == 4) {
-    const in_u8x4 px = *reinterpret_cast<const in_u8x4*>(img + src);
-    in_f32x4 r;
+    const u8x4 px = *reinterpret_cast<const u8x4*>(img + src);
+    f32x4 r;
 #pragma unroll
     for (int k = 0; k < 4; k++) r[k] = ((float)px[k] * IMG_INV255 - m) / sd;
-    *reinterpret_cast<in_f32x4*>(out + dst) = r;
+    *reinterpret_cast<f32x4*>(out + dst) = r;
   } else {
     out[dst] = ((float)img[src] * IMG_INV255 - m) / sd;
   }

@@ -35,8 +35,6 @@ constexpr int KG_CTX_PIX = LGU_KANGRU_CTX_PIXELS;  // pixels per context workgro
 constexpr int KG_TILE = 64;                        // pixels per LDS tile (4 MFMA column tiles)
 constexpr int KG_MT = 16;                          // edges per heads workgroup
 
-typedef float kg_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 kg_f16x8 __attribute__((ext_vector_type(8)));
 
 template <typename T> __device__ __forceinline__ float rnd(float v) { return (float)(T)v; }
 __device__ __forceinline__ float kg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -47,9 +45,9 @@ __device__ __forceinline__ float kg_sigmoid(float v) { return 1.0f / (1.0f + exp
 template <typename T> struct KgMma;
 template <> struct KgMma<_Float16> {
   static constexpr int KS = 32;  // k per instruction
-  typedef kg_f16x8 frag;
+  typedef f16x8 frag;
   static __device__ __forceinline__ frag ld(const _Float16* p) { return *reinterpret_cast<const frag*>(p); }
-  static __device__ __forceinline__ kg_f32x4 mma(frag a, frag b, kg_f32x4 c) {
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
   static constexpr int kofs(int kg) { return 8 * kg; }
@@ -58,7 +56,7 @@ template <> struct KgMma<float> {
   static constexpr int KS = 4;
   typedef float frag;
   static __device__ __forceinline__ frag ld(const float* p) { return *p; }
-  static __device__ __forceinline__ kg_f32x4 mma(frag a, frag b, kg_f32x4 c) {
+  static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
   }
   static constexpr int kofs(int kg) { return kg; }
@@ -142,7 +140,7 @@ __global__ __launch_bounds__(KG_THREADS) void kangru_context_kernel(const T* __r
       for (int ks = 0; ks < NKS; ks++) b[ks] = M::ld(tile + p * PITCH + ks * M::KS + M::kofs(kg));
 #pragma unroll
       for (int ct = 0; ct < 2; ct++) {
-        kg_f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int ks = 0; ks < NKS; ks++) acc = M::mma(a[ct][ks], b[ks], acc);
 #pragma unroll
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(KG_THREADS) void kan_heads_kernel(const T* __restri
   for (int nt = 0; nt < 2; nt++) {
     const int o = 32 * w + 16 * nt + lr;
     const T* wrow = wpack + ((size_t)h * KG_C + o) * KG_K + M::kofs(kg);
-    kg_f32x4 accb = {0.0f, 0.0f, 0.0f, 0.0f}, accs = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 accb = {0.0f, 0.0f, 0.0f, 0.0f}, accs = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int k0 = 0; k0 < KG_C; k0 += M::KS) accb = M::mma(M::ld(arow + k0), M::ld(wrow + k0), accb);
 #pragma unroll 8

@@ -51,9 +51,22 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   return v;
 }
 
-// ---- packed int16 pairs (x low, y high): one v_pk_min_i16 / v_pk_max_i16 serves both axes
+// ---- vector types: the one definition of each (ext_vector_type: element access with [], bit casts, 16-byte loads).
+// f32x4 rather than HIP's float4 struct where a loop-carried array of them must stay in registers.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));  // a pair at any element address
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // e.g. a fragment as the four dwords it is loaded as
+typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
 typedef short __attribute__((ext_vector_type(2))) short2v;
 
+// ---- packed int16 pairs (x low, y high): one v_pk_min_i16 / v_pk_max_i16 serves both axes
 __device__ __forceinline__ int pk16(int x, int y) { return (x & 0xffff) | (y << 16); }
 __device__ __forceinline__ int pk_lo(int v) { return (int)(short)(v & 0xffff); }
 __device__ __forceinline__ int pk_hi(int v) { return v >> 16; }
@@ -65,10 +78,10 @@ __device__ __forceinline__ int pk_max(int a, int b) {
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// Wave-wide packed min/max: DPP inside each row of 16 lanes (xor 1, xor 2, half-mirror,
-// mirror), then the four row results are read with v_readlane and combined (wave-uniform).
+// Packed min/max over each ROW of 16 lanes (every lane of the row gets the row's result): DPP xor 1, xor 2,
+// half-mirror, mirror.
 template <bool IS_MIN>
-__device__ __forceinline__ int wave_pk_reduce(int v) {
+__device__ __forceinline__ int row16_pk_reduce(int v) {
 #define LGU_DPP_STEP(ctrl)                                                  \
   {                                                                         \
     const int o = __builtin_amdgcn_update_dpp(v, v, ctrl, 0xf, 0xf, false); \
@@ -79,6 +92,14 @@ __device__ __forceinline__ int wave_pk_reduce(int v) {
   LGU_DPP_STEP(0x141)  // row_half_mirror
   LGU_DPP_STEP(0x140)  // row_mirror
 #undef LGU_DPP_STEP
+  return v;
+}
+
+// Wave-wide packed min/max: the row reduction, then the four row results are read with v_readlane and combined
+// (wave-uniform).
+template <bool IS_MIN>
+__device__ __forceinline__ int wave_pk_reduce(int v) {
+  v = row16_pk_reduce<IS_MIN>(v);
   const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
   const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
   return IS_MIN ? pk_min(pk_min(r0, r1), pk_min(r2, r3)) : pk_max(pk_max(r0, r1), pk_max(r2, r3));

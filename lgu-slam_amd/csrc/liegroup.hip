@@ -31,7 +31,6 @@ constexpr int LIE_THREADS = 256;
 constexpr int LIE_CHUNK = 12;                               // floats per lane of the 12-float stream
 constexpr int LIE_BLOCK_FLOATS = LIE_THREADS * LIE_CHUNK;   // 3072: a multiple of 3, 4 and 6
 
-typedef float lie_f4 __attribute__((ext_vector_type(4)));
 
 enum { LIE_INV, LIE_MUL, LIE_RETR, LIE_EXP, LIE_LOG, LIE_MATRIX };
 enum { LIE_ACT3, LIE_ADJ, LIE_ADJT };
@@ -204,11 +203,11 @@ __global__ __launch_bounds__(LIE_ELEM_THREADS) void lie_elem_kernel(const float*
     for (int m = 0; m < T; m++) out[(size_t)i * T + m] = v[m];
   } else {  // LIE_MATRIX: [[R, t], [0, 1]] row-major, four 16-byte stores (out is 64-byte aligned per element)
     const float x = q[0], y = q[1], z = q[2], w = q[3];
-    lie_f4* M = reinterpret_cast<lie_f4*>(out + (size_t)i * 16);
-    M[0] = lie_f4{1.0f - 2.0f * (y * y + z * z), 2.0f * (x * y - z * w), 2.0f * (x * z + y * w), t[0]};
-    M[1] = lie_f4{2.0f * (x * y + z * w), 1.0f - 2.0f * (x * x + z * z), 2.0f * (y * z - x * w), t[1]};
-    M[2] = lie_f4{2.0f * (x * z - y * w), 2.0f * (y * z + x * w), 1.0f - 2.0f * (x * x + y * y), t[2]};
-    M[3] = lie_f4{0.0f, 0.0f, 0.0f, 1.0f};
+    f32x4* M = reinterpret_cast<f32x4*>(out + (size_t)i * 16);
+    M[0] = f32x4{1.0f - 2.0f * (y * y + z * z), 2.0f * (x * y - z * w), 2.0f * (x * z + y * w), t[0]};
+    M[1] = f32x4{2.0f * (x * y + z * w), 1.0f - 2.0f * (x * x + z * z), 2.0f * (y * z - x * w), t[1]};
+    M[2] = f32x4{2.0f * (x * z - y * w), 2.0f * (y * z + x * w), 1.0f - 2.0f * (x * x + y * y), t[2]};
+    M[3] = f32x4{0.0f, 0.0f, 0.0f, 1.0f};
   }
 }
 
@@ -226,18 +225,18 @@ __global__ __launch_bounds__(LIE_THREADS) void lie_act4_kernel(const float* __re
   if (row >= rows) return;
   float t[3], q[4];
   load_elem<K>(G + group_of(row, g_div, narrow) * K, t, q);
-  lie_f4 p;
+  f32x4 p;
   if (VEC) {
-    p = reinterpret_cast<const lie_f4*>(in)[row];
+    p = reinterpret_cast<const f32x4*>(in)[row];
   } else {
-    p = lie_f4{in[row * 4], in[row * 4 + 1], in[row * 4 + 2], in[row * 4 + 3]};
+    p = f32x4{in[row * 4], in[row * 4 + 1], in[row * 4 + 2], in[row * 4 + 3]};
   }
   const float X[3] = {p.x, p.y, p.z};
   float Y[3];
   act_so3(q, X, Y);
-  const lie_f4 r = {Y[0] + t[0] * p.w, Y[1] + t[1] * p.w, Y[2] + t[2] * p.w, p.w};
+  const f32x4 r = {Y[0] + t[0] * p.w, Y[1] + t[1] * p.w, Y[2] + t[2] * p.w, p.w};
   if (VEC) {
-    reinterpret_cast<lie_f4*>(out)[row] = r;
+    reinterpret_cast<f32x4*>(out)[row] = r;
   } else {
     out[row * 4] = r.x; out[row * 4 + 1] = r.y; out[row * 4 + 2] = r.z; out[row * 4 + 3] = r.w;
   }
@@ -292,7 +291,7 @@ __global__ __launch_bounds__(LIE_THREADS) void lie_stream12_kernel(const float* 
     for (int j = 0; j < 3; j++) {
       const int idx = (tid + j * LIE_THREADS) * 4;
       if (idx + 3 < cnt) {
-        *reinterpret_cast<lie_f4*>(sh + idx) = *reinterpret_cast<const lie_f4*>(in + base + idx);
+        *reinterpret_cast<f32x4*>(sh + idx) = *reinterpret_cast<const f32x4*>(in + base + idx);
       } else {
         for (int m = 0; m < 4; m++)
           if (idx + m < cnt) sh[idx + m] = in[base + idx + m];
@@ -308,8 +307,8 @@ __global__ __launch_bounds__(LIE_THREADS) void lie_stream12_kernel(const float* 
   __syncthreads();
   const long long row0 = base / W + (long long)tid * RPT;
   if (row0 < rows) {
-    lie_f4* mine = reinterpret_cast<lie_f4*>(sh + tid * LIE_CHUNK);
-    const lie_f4 a0 = mine[0], a1 = mine[1], a2 = mine[2];
+    f32x4* mine = reinterpret_cast<f32x4*>(sh + tid * LIE_CHUNK);
+    const f32x4 a0 = mine[0], a1 = mine[1], a2 = mine[2];
     float v[LIE_CHUNK] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
     long long have = -1;
     float t[3], q[4];
@@ -324,9 +323,9 @@ __global__ __launch_bounds__(LIE_THREADS) void lie_stream12_kernel(const float* 
         stream_row<OP, K>(t, q, v + r * W);
       }
     }
-    mine[0] = lie_f4{v[0], v[1], v[2], v[3]};
-    mine[1] = lie_f4{v[4], v[5], v[6], v[7]};
-    mine[2] = lie_f4{v[8], v[9], v[10], v[11]};
+    mine[0] = f32x4{v[0], v[1], v[2], v[3]};
+    mine[1] = f32x4{v[4], v[5], v[6], v[7]};
+    mine[2] = f32x4{v[8], v[9], v[10], v[11]};
   }
   __syncthreads();
   if (VEC) {
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(LIE_THREADS) void lie_stream12_kernel(const float* 
     for (int j = 0; j < 3; j++) {
       const int idx = (tid + j * LIE_THREADS) * 4;
       if (idx + 3 < cnt) {
-        *reinterpret_cast<lie_f4*>(out + base + idx) = *reinterpret_cast<const lie_f4*>(sh + idx);
+        *reinterpret_cast<f32x4*>(out + base + idx) = *reinterpret_cast<const f32x4*>(sh + idx);
       } else {
         for (int m = 0; m < 4; m++)
           if (idx + m < cnt) out[base + idx + m] = sh[idx + m];

@@ -15,7 +15,7 @@
 // LDS [tap][pixel] tile and writes 64-byte coalesced segments.
 // Summation over channels is a per-lane partial + wave tree instead of the reference's
 // sequential 32-channel chunks: equal up to fp32 rounding (tests: 1e-5).
-#include "lgu_common.hpp"
+#include "lowmem_family.hpp"
 
 namespace lgu {
 
@@ -25,12 +25,7 @@ constexpr int LM_MAXQ = 8;  // channels per lane: C <= 512
 
 __device__ __forceinline__ float wave_sum_dpp(float v) {
   // row-local xor/mirror steps on the VALU, then one cross-row butterfly
-#define LGU_SUM_STEP(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, false));
-  LGU_SUM_STEP(0xB1)
-  LGU_SUM_STEP(0x4E)
-  LGU_SUM_STEP(0x141)
-  LGU_SUM_STEP(0x140)
-#undef LGU_SUM_STEP
+  v = row16_sum(v);
   v += __shfl_xor(v, 16, kWave);
   v += __shfl_xor(v, 32, kWave);
   return v;
@@ -271,18 +266,9 @@ __global__ __launch_bounds__(LM_WAVES * kWave) void altcorr_bwd_kernel(const flo
   }
 }
 
-// lowmem_mfma.hip: fp32 matrix-core kernel (v_mfma_f32_16x16x4_f32); -1 = shape not served
-int lowmem_mfma_dispatch_f32(const float* fmap1, const float* fmap2, const float* coords, float* offset, float* corr,
-                             int B, int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st);
-// lowmem_tile.hip
-int lowmem_tile_dispatch(const float* fmap1, const float* fmap2, const float* coords, float* offset, float* corr, int B,
-                         int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st);
-
-static int check_fmap_args(const void* a, const void* b, const void* c, const void* d, int B, int S, int H1, int W1,
-                           int H2, int W2, int C, int radius) {
-  if (!a || !b || !c || !d) return LGU_E_BADARG;
-  if (B < 0 || S < 1 || H1 < 1 || W1 < 1 || H2 < 1 || W2 < 1 || C < 1 || radius < 0 || radius > LGU_MAX_RADIUS)
-    return LGU_E_BADARG;
+// What the float entries add to lowmem_entry_args(): the reference's own limits
+static int f32_entry_args(int C, int radius) {
+  if (radius > LGU_MAX_RADIUS) return LGU_E_BADARG;
   if (C % 32 != 0 || C > LM_MAXQ * kWave) return LGU_E_UNSUPPORTED;  // reference needs C % 32 == 0 too
   return LGU_OK;
 }
@@ -304,20 +290,22 @@ int lgu_lowmem_defsample_fwd_f32(const float* fmap1, const float* fmap2, const f
                                  float* corr, int B, int S, int H1, int W1, int H2, int W2, int C, int NO, int radius,
                                  void* stream) {
   using namespace lgu;
-  int rc = check_fmap_args(fmap1, fmap2, coords, corr, B, S, H1, W1, H2, W2, C, radius);
+  int rc = lowmem_entry_args({fmap1, fmap2, coords, corr}, B, S, H1, W1, &H2, &W2, 1, C, radius, kAnyOffsetRows);
+  if (rc == LGU_OK) rc = f32_entry_args(C, radius);
   if (rc != LGU_OK) return rc;
-  if (!offset || (long long)(B - 1) * (S - 1) >= (long long)NO) return LGU_E_BADARG;
+  if (!offset || !offset_rows_ok(B, S, NO)) return LGU_E_BADARG;
   if (B == 0) return LGU_OK;
+  const LowmemParams p = single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // LGU_LOWMEM_VARIANT (debug/A-B only): 0 = matrix-core kernel (fp32 MFMA), 2 = tile-staged VALU kernel,
   // 1 = wave-per-pixel kernel; each falls through to the next for shapes it does not serve
   const int variant = env_int("LGU_LOWMEM_VARIANT", 0);
   if (variant == 0) {
-    rc = lowmem_mfma_dispatch_f32(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, radius, st);
+    rc = lowmem_mfma_dispatch_f32(p, C, radius, st);
     if (rc >= 0) return rc;
   }
   if (variant == 0 || variant == 2) {
-    rc = lowmem_tile_dispatch(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, radius, st);
+    rc = lowmem_tile_dispatch(p, C, radius, st);
     if (rc >= 0) return rc;
   }
   const int nt = (2 * radius + 1) * (2 * radius + 1);
@@ -336,20 +324,22 @@ int lgu_lowmem_defsample_fwd_f32(const float* fmap1, const float* fmap2, const f
 int lgu_altcorr_fwd_f32(const float* fmap1, const float* fmap2, const float* coords, float* corr, int B, int S, int H1,
                         int W1, int H2, int W2, int C, int radius, void* stream) {
   using namespace lgu;
-  int rc = check_fmap_args(fmap1, fmap2, coords, corr, B, S, H1, W1, H2, W2, C, radius);
+  int rc = lowmem_entry_args({fmap1, fmap2, coords, corr}, B, S, H1, W1, &H2, &W2, 1, C, radius, kAnyOffsetRows);
+  if (rc == LGU_OK) rc = f32_entry_args(C, radius);
   if (rc != LGU_OK) return rc;
   if (radius > 3) return LGU_E_UNSUPPORTED;  // lattice (rd+1)^2 must fit one wave
   if (B == 0) return LGU_OK;
+  const LowmemParams p = single_level(fmap1, fmap2, coords, nullptr, corr, B, S, H1, W1, H2, W2);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // altcorr_forward == lowMem_defSample with zero offsets (same per-corner zero padding, same
   // [ix][iy] channel order): the tile-staged kernel serves it with a null offset pointer
   const int variant = env_int("LGU_LOWMEM_VARIANT", 0);
   if (variant == 0 && radius >= 1) {
-    rc = lowmem_mfma_dispatch_f32(fmap1, fmap2, coords, nullptr, corr, B, S, H1, W1, H2, W2, C, radius, st);
+    rc = lowmem_mfma_dispatch_f32(p, C, radius, st);
     if (rc >= 0) return rc;
   }
   if ((variant == 0 || variant == 2) && radius >= 1) {
-    rc = lowmem_tile_dispatch(fmap1, fmap2, coords, nullptr, corr, B, S, H1, W1, H2, W2, C, radius, st);
+    rc = lowmem_tile_dispatch(p, C, radius, st);
     if (rc >= 0) return rc;
   }
   const int nt = (2 * radius + 1) * (2 * radius + 1);
@@ -369,7 +359,8 @@ int lgu_altcorr_bwd_f32(const float* fmap1, const float* fmap2, const float* coo
                         float* fmap1_grad, float* fmap2_grad, int B, int S, int H1, int W1, int H2, int W2, int C,
                         int radius, void* stream) {
   using namespace lgu;
-  int rc = check_fmap_args(fmap1, fmap2, coords, corr_grad, B, S, H1, W1, H2, W2, C, radius);
+  int rc = lowmem_entry_args({fmap1, fmap2, coords, corr_grad}, B, S, H1, W1, &H2, &W2, 1, C, radius, kAnyOffsetRows);
+  if (rc == LGU_OK) rc = f32_entry_args(C, radius);
   if (rc != LGU_OK) return rc;
   if (!fmap1_grad || !fmap2_grad) return LGU_E_BADARG;
   if (radius > 3) return LGU_E_UNSUPPORTED;

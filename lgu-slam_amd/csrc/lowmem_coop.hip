@@ -25,12 +25,10 @@
 // Half products are exact in fp32 and the accumulation is fp32: the result differs from the `.float()` call site by
 // summation order only (tests: 1e-5).  Boxes wider than 16 (|offset| >= 4: never produced by corr.py:126-131) take the
 // per-tap fallback, as in lowmem_mfma.hip.
-#include "lgu_common.hpp"
+#include "lowmem_family.hpp"
 
 namespace lgu {
 
-typedef _Float16 cohalf8 __attribute__((ext_vector_type(8)));
-typedef float cof32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CO_SB = 2;                       // 4 x 4 sub-blocks per workgroup (tile = 4 rows x 8 columns of pixels)
 constexpr int CO_NW = 4;                       // waves per workgroup: two per sub-block in the box / sampling phases
@@ -40,43 +38,19 @@ constexpr int CO_BOXP = 18;                    // patch row pitch: 16 columns + 
 constexpr int CO_PP = 16 * CO_BOXP + 2;        // floats per patch (+2: consecutive pixels start 8 banks apart)
 constexpr int CO_GUARD = 20;                   // floats in front of the patches (>= CO_BOXP + 1): see the sampling phase
 constexpr int CO_OUTP = 4 * CO_QP + 4;          // output transpose pitch
-constexpr int CO_MAXL = 4;
 // Alignment mask of the tile window's first column: pairs of positions start at even columns (needed).  (Round 2 measured
 // 7 — fragment loads starting on 128-byte lines in the chunk-planar form: L2 read requests 4.22 -> 3.74 KB per pixel-level,
 // but the wider windows cost 2.5 % of time.)
 constexpr int CO_XALIGN = 1;
 constexpr int CO_LDS_FLOATS = CO_GUARD + CO_NPX * CO_PP + CO_NPX * 4 + 2 * CO_NW + 8;
 
-struct CoParams {
-  const _Float16* fmap1;
-  const _Float16* fmap2[CO_MAXL];
-  float* offset[CO_MAXL];   // null = zero offsets for that level
-  const float* coords;
-  float* corr;
-  int H2[CO_MAXL], W2[CO_MAXL];
-  int L, B, S, H1, W1, tiles_x, tiles_y, xcd_map, vec_out;
-  int lbase, lvl0, Ltot;
-  int f2_chunked;
-  // Work units.  The first n_fused workgroups serve ALL levels of their (edge, tile) in one wave life; the remaining
-  // n_split (edge, tile) items are served level group by level group (group k = levels gl0[k] .. gl0[k + 1] - 1), groups in
-  // launch order: n_fused is a whole number of rounds over the device's workgroup slots, and the short units fill the
-  // last, partial round (launch_coop).
-  int n_fused, n_split, ngroups, gl0[CO_MAXL + 1];
-  const long long* ii;
-  const long long* jj;
-  // Several reference calls in one launch (lgu_lowmem_pyramid_calls_fwd_h16): edge b samples with offset row orow[b] — the
-  // first edge of ITS call — instead of row b*n.  Null = one call.  Values are clamped to n_orow - 1 (no wild reads).
-  const int* orow;
-  int n_orow;
-};
-
 // one corner dot of one tap straight from memory (boxes larger than the patch): channels in order, as the reference sums
 // them.  One corner per call and not inlined: the rare path must not set the register count of the sampling phase.
 __device__ __noinline__ float co_corner_dot(const _Float16* f1p, const _Float16* f2p, int C, ptrdiff_t cstride) {
   float s = 0.f;
   for (int c = 0; c < C; c += 8) {
-    const cohalf8 f = *reinterpret_cast<const cohalf8*>(f1p + c);
-    const cohalf8 a = *reinterpret_cast<const cohalf8*>(f2p + (ptrdiff_t)(c / 8) * cstride);
+    const f16x8 f = *reinterpret_cast<const f16x8*>(f1p + c);
+    const f16x8 a = *reinterpret_cast<const f16x8*>(f2p + (ptrdiff_t)(c / 8) * cstride);
 #pragma unroll
     for (int i = 0; i < 8; i++) s = __builtin_fmaf((float)f[i], (float)a[i], s);
   }
@@ -90,21 +64,6 @@ __device__ __forceinline__ float4 co_corner_dots(const _Float16* f1p, const _Flo
   if (mask & 4) q.z = co_corner_dot(f1p, F2 + (pos11 + W2) * pstride, C, cstride);
   if (mask & 8) q.w = co_corner_dot(f1p, F2 + (pos11 + W2 + 1) * pstride, C, cstride);
   return q;
-}
-
-template <bool IS_MIN>
-__device__ __forceinline__ int co_row_pk_reduce(int v) {
-#define LGU_DPP_STEP(ctrl)                                                  \
-  {                                                                         \
-    const int o = __builtin_amdgcn_update_dpp(v, v, ctrl, 0xf, 0xf, false); \
-    v = IS_MIN ? pk_min(v, o) : pk_max(v, o);                               \
-  }
-  LGU_DPP_STEP(0xB1)
-  LGU_DPP_STEP(0x4E)
-  LGU_DPP_STEP(0x141)
-  LGU_DPP_STEP(0x140)
-#undef LGU_DPP_STEP
-  return v;
 }
 
 #ifdef LGU_MM_STAMPS
@@ -145,14 +104,14 @@ __device__ unsigned long long* g_co_stamps;  // [workgroup][wave][8 per level]
 #endif
 constexpr int CO_WPS = CO_WPS_N;
 template <int R, int KS>
-__global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const CoParams p_arg) {
+__global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const LowmemParams p_arg) {
   // The parameter block is read where it lies (the kernarg segment: the only argument, at offset 0), so per-level
   // fields are scalar loads at a computed offset instead of select chains over registers that do not fit the SGPR file.
-  typedef const CoParams __attribute__((address_space(4))) CoParamsK;
-  CoParamsK& p = *(CoParamsK*)__builtin_amdgcn_kernarg_segment_ptr();
+  typedef const LowmemParams __attribute__((address_space(4))) LowmemParamsK;
+  LowmemParamsK& p = *(LowmemParamsK*)__builtin_amdgcn_kernarg_segment_ptr();
   (void)p_arg;
   typedef _Float16 T;
-  typedef cohalf8 frag;
+  typedef f16x8 frag;
   constexpr int CPS = 32, EPL = 8;
   constexpr int RD = 2 * R + 1, NT = RD * RD, C = CPS * KS;
   constexpr int TI = (NT + 15) / 16;
@@ -189,7 +148,7 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
   const int px0 = bx * (4 * CO_SB) + msb * 4;  // first pixel column of this wave's sub-block
   const size_t HW1 = (size_t)H1 * W1;
   const size_t f1i = p.ii ? (size_t)p.ii[b] : (size_t)b, f2i = p.jj ? (size_t)p.jj[b] : (size_t)b;
-  const T* const F1 = p.fmap1 + f1i * HW1 * C;
+  const T* const F1 = static_cast<const T*>(p.fmap1) + f1i * HW1 * C;
   const float2* const cbase = reinterpret_cast<const float2*>(p.coords) + ((size_t)b * S + n) * HW1;
 
   // Levels are served coarse to fine.  A level's offsets (16 registers) are requested one step ahead of their use: right
@@ -257,7 +216,7 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
   // (Serving the two zero-offset levels in one box / sweep / sampling pass — their 8-row patches fit one 16-row patch — was
   // built and measured: two barriers less per wave life, but 109 against 105 us; the levels stay one pass each.)
   for (int lvl = lv1 - 1; lvl >= lv0; lvl--) {
-    const T* const fmap2 = p.fmap2[lvl];
+    const T* const fmap2 = static_cast<const T*>(p.fmap2[lvl]);
     const int H2 = p.H2[lvl], W2 = p.W2[lvl];
     const float cscale = __builtin_ldexpf(1.0f, -(p.lbase + lvl));
     const T* const F2 = fmap2 + f2i * H2 * W2 * C;
@@ -314,8 +273,8 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
             y0 = fminf(y0, wy); y1 = fmaxf(y1, wy);
           }
           // saturating conversion: absurd or non-finite coords give a box that fails the size test below
-          lo = co_row_pk_reduce<true>(__builtin_bit_cast(int, __builtin_amdgcn_cvt_pk_i16((int)x0, (int)y0)));
-          hi = co_row_pk_reduce<false>(__builtin_bit_cast(int, __builtin_amdgcn_cvt_pk_i16((int)x1, (int)y1)));
+          lo = row16_pk_reduce<true>(__builtin_bit_cast(int, __builtin_amdgcn_cvt_pk_i16((int)x0, (int)y0)));
+          hi = row16_pk_reduce<false>(__builtin_bit_cast(int, __builtin_amdgcn_cvt_pk_i16((int)x1, (int)y1)));
         }
         const int xlo = pk_lo(lo), ylo = pk_hi(lo), xhi = pk_lo(hi) + 1, yhi = pk_hi(hi) + 1;  // + 1: the right / bottom corners
         const bool any = pv && xhi > xlo && yhi > ylo;
@@ -431,9 +390,9 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
           for (int it = 0; it < nit; it += PF) {
 #pragma unroll
             for (int j = 0; j < PF; j++) {
-              cof32x4 d[CO_SB];
+              f32x4 d[CO_SB];
 #pragma unroll
-              for (int m = 0; m < CO_SB; m++) d[m] = cof32x4{0.f, 0.f, 0.f, 0.f};
+              for (int m = 0; m < CO_SB; m++) d[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
               for (int s = 0; s < KS; s++)
 #pragma unroll
@@ -613,7 +572,7 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
 #undef CO_FRESH_LANE
 
 template <int R, int KS>
-static int launch_coop(CoParams p, hipStream_t st) {
+static int launch_coop(LowmemParams p, hipStream_t st) {
   auto kern = lowmem_coop_kernel<R, KS>;
   // LGU_LOWMEM_COOP_LDS_PAD (debug / diagnosis only): extra dynamic LDS in KB per workgroup, clamped to the 160 KB of a CU —
   // fewer resident workgroups per CU, to read a workgroup's life against the number of workgroups sharing the CU
@@ -634,7 +593,7 @@ static int launch_coop(CoParams p, hipStream_t st) {
     if (p.offset[l]) l++;
     else while (l < p.L && !p.offset[l]) l++;
   }
-  for (int k = p.ngroups; k <= CO_MAXL; k++) p.gl0[k] = p.L;
+  for (int k = p.ngroups; k <= LOWMEM_MAXL; k++) p.gl0[k] = p.L;
   // Fused workgroups in whole rounds over the device's slots (4 resident workgroups per CU), the remainder split by
   // level group so that the last round is made of short units: a call of 2.3 rounds costs ~2.4 instead of 3.
   // LGU_LOWMEM_COOP_SPLIT (debug / A-B only): 0 = all fused, 1 = all split, default = the rule above.
@@ -659,34 +618,14 @@ static int launch_coop(CoParams p, hipStream_t st) {
 
 // Serves half feature maps with C in {32, 64, 128} and radius 1..3; returns -1 otherwise (the caller then takes the
 // one-wave-per-block kernel of lowmem_mfma.hip).  LGU_LOWMEM_COOP=0 (debug / A-B only) disables it.
-int lowmem_coop_dispatch(const void* fmap1, const void* const* fmap2, float* const* offset, const float* coords, float* corr,
-                         const int* H2, const int* W2, int L, int B, int S, int H1, int W1, int C, int radius, int lbase,
-                         int lvl0, int Ltot, int f2_chunked, const long long* ii, const long long* jj, const int* orow, int n_orow,
-                         hipStream_t st) {
+int lowmem_coop_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) {
   if (env_int("LGU_LOWMEM_COOP", 1) == 0) return -1;
-  if (orow && (S != 1 || n_orow < 1)) return -1;
-  if (L < 1 || L > CO_MAXL || radius < 1 || radius > 3 || S > 65535) return -1;
+  if (p.orow && (p.S != 1 || p.n_orow < 1)) return -1;
   // a single zero-offset level (altcorr_forward; the r = 1 probe of AltCorrBlock) has little window to share and no
   // offsets to wait for: the independent waves of the one-wave kernel serve it faster (probe: 18 against 25 us)
-  if (L == 1 && !offset[0] && env_int("LGU_LOWMEM_COOP_SINGLE", 0) == 0) return -1;
-  uintptr_t al = reinterpret_cast<uintptr_t>(fmap1);
-  for (int l = 0; l < L; l++) al |= reinterpret_cast<uintptr_t>(fmap2[l]);
-  uintptr_t al8 = reinterpret_cast<uintptr_t>(coords);  // coords and offsets (null = none) go as 8-byte (x, y) pairs
-  for (int l = 0; l < L; l++) al8 |= reinterpret_cast<uintptr_t>(offset[l]);
-  if ((al & 15) != 0 || (al8 & 7) != 0) return -1;
-  if ((size_t)H1 * W1 * C >= (1u << 31) || (size_t)H1 * W1 * 49 * 8 >= (1ull << 32)) return -1;
-  CoParams p = {};
-  p.fmap1 = static_cast<const _Float16*>(fmap1);
-  for (int l = 0; l < L; l++) {
-    if ((size_t)H2[l] * W2[l] * C >= (1u << 31) || H2[l] > 32767 || W2[l] > 32767) return -1;
-    p.fmap2[l] = static_cast<const _Float16*>(fmap2[l]);
-    p.offset[l] = offset[l];
-    p.H2[l] = H2[l]; p.W2[l] = W2[l];
-  }
-  p.coords = coords; p.corr = corr;
-  p.L = L; p.B = B; p.S = S; p.H1 = H1; p.W1 = W1;
-  p.lbase = lbase; p.lvl0 = lvl0; p.Ltot = Ltot; p.f2_chunked = f2_chunked; p.ii = ii; p.jj = jj;
-  p.orow = orow; p.n_orow = n_orow;
+  if (p.L == 1 && !p.offset[0] && env_int("LGU_LOWMEM_COOP_SINGLE", 0) == 0) return -1;
+  if (!lowmem_matrix_serves(p, C, radius)) return -1;
+  if ((size_t)p.H1 * p.W1 * 49 * 8 >= (1ull << 32)) return -1;  // 32-bit byte offsets into one offset row and one output level
 #define LGU_CO_CASE(RV, KSV) \
   if (radius == RV && C == 32 * KSV) return launch_coop<RV, KSV>(p, st);
   LGU_CO_CASE(3, 4) LGU_CO_CASE(1, 4) LGU_CO_CASE(2, 4)
@@ -704,8 +643,12 @@ extern "C" {
 int lgu_co_diag_set_stamps(void* q) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(lgu::g_co_stamps), &q, sizeof(q)); }
 int lgu_co_diag_pyramid(const void* fmap1, const void* const* fmap2, float* const* offset, const float* coords, float* corr,
                         const int* H2, const int* W2, int L, int B, int S, int H1, int W1, int C, int radius, int chunked) {
-  return lgu::lowmem_coop_dispatch(fmap1, fmap2, offset, coords, corr, H2, W2, L, B, S, H1, W1, C, radius, 0, 0, L, chunked,
-                                   nullptr, nullptr, nullptr, 0, nullptr);
+  if (!fmap2 || !offset || !H2 || !W2 || L < 1 || L > lgu::LOWMEM_MAXL) return -1;
+  lgu::LowmemParams p = lgu::single_level(fmap1, fmap2[0], coords, offset[0], corr, B, S, H1, W1, H2[0], W2[0]);
+  for (int l = 1; l < L; l++) { p.fmap2[l] = fmap2[l]; p.offset[l] = offset[l]; p.H2[l] = H2[l]; p.W2[l] = W2[l]; }
+  p.L = p.Ltot = L;
+  p.f2_chunked = chunked;
+  return lgu::lowmem_coop_dispatch(p, C, radius, nullptr);
 }
 }
 #endif

@@ -25,12 +25,10 @@
 // so that neighbouring windows share L1/L2 lines, and edges are dealt to XCDs (workgroup id % 8) so one
 // edge's fmap2 (a few MB) stays in one XCD's L2.
 // Pixels whose box exceeds 16x16 (|offset| >= 4: never produced by corr.py:126-131) take a per-tap fallback.
-#include "lgu_common.hpp"
+#include "lowmem_family.hpp"
 
 namespace lgu {
 
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int MM_BP = 16;            // pixels per wave = 4 x 4 block (MFMA rows)
 constexpr int MM_BOX = 16;           // patch row pitch / largest box side
@@ -53,9 +51,9 @@ __host__ __device__ constexpr int mm_lds_floats(int MT, bool ZO = false) {
 // tile kernel).
 template <typename T> struct MmT;
 template <> struct MmT<_Float16> {
-  typedef half8v frag;
+  typedef f16x8 frag;
   static constexpr int CPS = 32, EPL = 8;
-  static __device__ __forceinline__ f32x4v mma(const frag& a, const frag& b, f32x4v d) {
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, f32x4 d) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, d, 0, 0, 0);
   }
   static __device__ __forceinline__ float dot(const frag& f, const frag& a, float s) {
@@ -65,9 +63,9 @@ template <> struct MmT<_Float16> {
   }
 };
 template <> struct MmT<float> {
-  typedef f32x4v frag;
+  typedef f32x4 frag;
   static constexpr int CPS = 16, EPL = 4;
-  static __device__ __forceinline__ f32x4v mma(const frag& a, const frag& b, f32x4v d) {
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, f32x4 d) {
 #pragma unroll
     for (int t = 0; t < 4; t++) d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[t], d, 0, 0, 0);
     return d;
@@ -81,7 +79,7 @@ template <> struct MmT<float> {
 
 // Fallback for boxes larger than the patch: the four corner dots of one tap straight from memory.  F2 is addressed
 // as position * pstride + chunk * cstride (+ element in chunk): channel-last maps have pstride = C, cstride = EPL; the
-// chunk-planar form (MmParams::f2_chunked) has pstride = EPL, cstride = H2 * W2 * EPL.
+// chunk-planar form (LowmemParams::f2_chunked) has pstride = EPL, cstride = H2 * W2 * EPL.
 template <typename T>
 __device__ __noinline__ float4 corner_dots(const T* f1p, const T* F2, ptrdiff_t pos11, int C, int W2, int mask,
                                            ptrdiff_t pstride, ptrdiff_t cstride) {
@@ -99,22 +97,6 @@ __device__ __noinline__ float4 corner_dots(const T* f1p, const T* F2, ptrdiff_t 
   return make_float4(q11, q21, q12, q22);
 }
 
-// Packed (x low, y high) int16 min / max over each ROW of 16 lanes (every lane of the row gets the result).
-template <bool IS_MIN>
-__device__ __forceinline__ int row_pk_reduce(int v) {
-#define LGU_DPP_STEP(ctrl)                                                  \
-  {                                                                         \
-    const int o = __builtin_amdgcn_update_dpp(v, v, ctrl, 0xf, 0xf, false); \
-    v = IS_MIN ? pk_min(v, o) : pk_max(v, o);                               \
-  }
-  LGU_DPP_STEP(0xB1)   // quad_perm:[1,0,3,2]
-  LGU_DPP_STEP(0x4E)   // quad_perm:[2,3,0,1]
-  LGU_DPP_STEP(0x141)  // row_half_mirror
-  LGU_DPP_STEP(0x140)  // row_mirror
-#undef LGU_DPP_STEP
-  return v;
-}
-
 // Diagnostic builds only (tools/diag/run_mm_stamps.py defines LGU_MM_STAMPS): per-wave phase stamps.
 #ifdef LGU_MM_STAMPS
 __device__ unsigned long long* g_mm_stamps;  // [wave][8]
@@ -126,34 +108,7 @@ __device__ unsigned long long* g_mm_stamps;  // [wave][8]
 #define MM_STAMP(i)
 #endif
 
-constexpr int MM_MAXL = 4;  // pyramid levels one launch can serve
-
-// Launch parameters.  L == 1: one operator call (lowMem_defSample / altcorr_forward).  L > 1: the per-level loop of
-// AltCorrBlock.corr_fn (reference corr.py:192-213) in ONE launch: work items are (level, edge, block) with level 0
-// (the largest windows) first, level l samples fmap2[l] at coords / 2^l with offset[l] and writes channels
-// l*NT .. (l+1)*NT - 1 of the concatenated output.
-struct MmParams {
-  const void* fmap1;  // element type = the kernel's T (half or float)
-  const void* fmap2[MM_MAXL];
-  float* offset[MM_MAXL];  // null = zero offsets for that level (altcorr)
-  const float* coords;
-  float* corr;
-  int H2[MM_MAXL], W2[MM_MAXL];
-  int L, B, S, H1, W1, blocks_x, blocks_y, xcd_map, vec_out;
-  int lbase;             // pyramid level of fmap2[0]: level l of the launch samples at coords / 2^(lbase + l)
-  int lvl0, Ltot;        // output: level l of this launch writes channels (lvl0 + l) * NT .. of Ltot * NT (a pyramid call may be
-                         // split into a launch for the levels with offsets and one for the zero-offset levels)
-  // fmap2 storage.  0: channel-last (F,H2,W2,C), the operators' layout.  1: chunk-planar (F, C/EPL, H2, W2, EPL) with
-  // EPL = 16 bytes of channels: the 16 x-adjacent positions an MFMA B fragment covers are then 256 CONTIGUOUS bytes per
-  // 16-byte channel chunk, where channel-last puts them 2C bytes apart.  The vector L1 serves a load quad by quad
-  // (4 lanes), one access per distinct 128-byte line in the quad: 64 accesses per fragment load channel-last, 16-20
-  // chunk-planar — the access rate, not L2 bandwidth, is what bounds the sweep (AltCorrBlock keeps its pyramid in this form).
-  int f2_chunked;
-  const long long* ii;   // optional frame indices (device, int64): edge b reads fmap1[ii[b]] and fmap2[l][jj[b]]
-  const long long* jj;   // straight from the frame buffers — no gathered per-edge copies; null = fmap*[b]
-  const int* orow;       // optional (device, B ints; cooperative kernel only): offset row of edge b, see lgu_lowmem_pyramid_calls_fwd_h16
-  int n_orow;
-};
+constexpr int MM_MAXL = LOWMEM_MAXL;
 
 // One wave = one workgroup = a block of MT 4 x 4 pixel sub-blocks side by side (4 rows x 4 MT columns).  Every B
 // fragment (16 window positions x all channels) fetched by the sweep feeds MT MFMA row tiles, and the union window of
@@ -170,7 +125,7 @@ struct MmParams {
 // (no offsets held across the sweep) doubles the resident waves, which is what these overhead-bound levels need
 // (their sweep is 2-3 us of an 11 us wave life: tools/diag/run_mm_stamps.py).
 template <int R, int KS, typename T, int MT, bool ZO>
-__global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma_kernel(const MmParams p) {
+__global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma_kernel(const LowmemParams p) {
   typedef typename MmT<T>::frag frag;
   constexpr int CPS = MmT<T>::CPS, EPL = MmT<T>::EPL;
   constexpr int RD = 2 * R + 1, NT = RD * RD, C = CPS * KS;
@@ -188,11 +143,11 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
   int* const pbox = reinterpret_cast<int*>(patch + NP * PP);          // [NP][xlo,ylo,bw,bh]
   const int lane = threadIdx.x;
   const int lx = lane & 15, lg = lane >> 4;
-  const int B = p.B, S = p.S, H1 = p.H1, W1 = p.W1, blocks_x = p.blocks_x;
+  const int B = p.B, S = p.S, H1 = p.H1, W1 = p.W1, blocks_x = p.tiles_x;
 
   // ---- workgroup -> (level, edge, block) ----
   int b, blk;
-  const int blocks = blocks_x * p.blocks_y;
+  const int blocks = blocks_x * p.tiles_y;
   const int per_level = (p.xcd_map ? ((B + 7) >> 3) * 8 : B) * blocks;
   const int lvl = p.L > 1 ? (int)blockIdx.x / per_level : 0;
   const int item = p.L > 1 ? (int)blockIdx.x - lvl * per_level : (int)blockIdx.x;
@@ -303,8 +258,8 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
           lo = part ? pk_min(lo, pk16(xa, ya)) : lo;
           hi = part ? pk_max(hi, pk16(xb, yb)) : hi;
         }
-        lo = row_pk_reduce<true>(lo);
-        hi = row_pk_reduce<false>(hi);
+        lo = row16_pk_reduce<true>(lo);
+        hi = row16_pk_reduce<false>(hi);
       }
       const int xlo = pk_lo(lo), ylo = pk_hi(lo), xhi = pk_lo(hi), yhi = pk_hi(hi);
       const bool any = xhi >= xlo && yhi >= ylo;
@@ -386,10 +341,10 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
 #pragma unroll
       for (int j = 0; j < MM_PF; j++) {
         if (it + j < nit) {  // wave-uniform
-          f32x4v d[MT];
+          f32x4 d[MT];
 #pragma unroll
           for (int m = 0; m < MT; m++) {
-            d[m] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            d[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int s = 0; s < KS; s++) d[m] = MmT<T>::mma(a[m][s], bq[j][s], d[m]);
           }
@@ -526,12 +481,12 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
 }
 
 template <int R, int KS, typename T, int MT, bool ZO>
-static int launch_mfma_mt(MmParams p, hipStream_t st) {
+static int launch_mfma_mt(LowmemParams p, hipStream_t st) {
   const size_t lds = sizeof(float) * (size_t)mm_lds_floats(MT, ZO);
   auto kern = lowmem_mfma_kernel<R, KS, T, MT, ZO>;
-  p.blocks_x = (p.W1 + 4 * MT - 1) / (4 * MT);
-  p.blocks_y = (p.H1 + 3) / 4;
-  const int blocks = p.blocks_x * p.blocks_y;
+  p.tiles_x = (p.W1 + 4 * MT - 1) / (4 * MT);
+  p.tiles_y = (p.H1 + 3) / 4;
+  const int blocks = p.tiles_x * p.tiles_y;
   p.xcd_map = p.B >= 8 ? 1 : 0;
   const size_t nwg = (size_t)p.L * (p.xcd_map ? (size_t)((p.B + 7) / 8) * 8 * blocks : (size_t)p.B * blocks);
   if (nwg >= (1u << 31)) return -1;
@@ -550,7 +505,7 @@ static int launch_mfma_mt(MmParams p, hipStream_t st) {
 // (Running the two launches of a call concurrently — the second on a side stream forked and joined with events — was
 // measured and lost: 163.5 vs 146.3 us for config 4; the launches stay in order on the caller's stream.)
 template <int R, int KS, typename T>
-static int launch_mfma(const MmParams& p, hipStream_t st) {
+static int launch_mfma(const LowmemParams& p, hipStream_t st) {
   const bool mt2 = env_int("LGU_LOWMEM_MT", 1) >= 2 && p.W1 > 4;
   const bool zo_on = env_int("LGU_LOWMEM_ZO", 1) != 0;
   int l0 = 0;
@@ -558,7 +513,7 @@ static int launch_mfma(const MmParams& p, hipStream_t st) {
     const bool zo = zo_on && p.offset[l0] == nullptr;
     int l1 = l0 + 1;
     while (l1 < p.L && (zo_on && p.offset[l1] == nullptr) == zo) l1++;
-    MmParams q = p;
+    LowmemParams q = p;
     q.L = l1 - l0;
     q.lbase = p.lbase + l0;
     q.lvl0 = p.lvl0 + l0;
@@ -578,28 +533,15 @@ static int launch_mfma(const MmParams& p, hipStream_t st) {
   return LGU_OK;
 }
 
-// lowmem_coop.hip: four waves share the swept windows, all levels in one wave life (half maps, C <= 128)
-int lowmem_coop_dispatch(const void* fmap1, const void* const* fmap2, float* const* offset, const float* coords, float* corr,
-                         const int* H2, const int* W2, int L, int B, int S, int H1, int W1, int C, int radius, int lbase,
-                         int lvl0, int Ltot, int f2_chunked, const long long* ii, const long long* jj, const int* orow, int n_orow,
-                         hipStream_t st);
-
+// The cooperative kernel first (half maps); -1 when neither matrix-core kernel serves the block.
 template <typename T>
-static int mfma_dispatch(const MmParams& p, int C, int radius, hipStream_t st) {
+static int mfma_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    const int rc = lowmem_coop_dispatch(p.fmap1, p.fmap2, p.offset, p.coords, p.corr, p.H2, p.W2, p.L, p.B, p.S, p.H1, p.W1, C,
-                                        radius, p.lbase, p.lvl0, p.Ltot, p.f2_chunked, p.ii, p.jj, p.orow, p.n_orow, st);
+    const int rc = lowmem_coop_dispatch(p, C, radius, st);
     if (rc >= 0) return rc;
   }
   if (p.orow) return -1;  // only the cooperative kernel knows offset rows per edge
-  uintptr_t al = reinterpret_cast<uintptr_t>(p.fmap1);
-  for (int l = 0; l < p.L; l++) al |= reinterpret_cast<uintptr_t>(p.fmap2[l]);
-  uintptr_t al8 = reinterpret_cast<uintptr_t>(p.coords);  // coords and offsets (null = none) go as 8-byte (x, y) pairs
-  for (int l = 0; l < p.L; l++) al8 |= reinterpret_cast<uintptr_t>(p.offset[l]);
-  if (radius < 1 || radius > 3 || (al & 15) != 0 || (al8 & 7) != 0 || p.S > 65535) return -1;
-  if ((size_t)p.H1 * p.W1 * C >= (1u << 31)) return -1;
-  for (int l = 0; l < p.L; l++)
-    if ((size_t)p.H2[l] * p.W2[l] * C >= (1u << 31) || p.H2[l] > 32767 || p.W2[l] > 32767) return -1;
+  if (!lowmem_matrix_serves(p, C, radius)) return -1;
   constexpr int cps = MmT<T>::CPS;  // half: C in {32,64,128,256}; float: C in {16,32,64,128}
 #define LGU_MM_CASE(RV, KSV) \
   if (radius == RV && C == cps * KSV) return launch_mfma<RV, KSV, T>(p, st);
@@ -611,24 +553,8 @@ static int mfma_dispatch(const MmParams& p, int C, int radius, hipStream_t st) {
   return -1;
 }
 
-// Return -1 when the matrix-core kernel does not serve the arguments (the caller then uses the VALU tile kernel).
-static MmParams single_level(const void* fmap1, const void* fmap2, const float* coords, float* offset, float* corr, int B,
-                             int S, int H1, int W1, int H2, int W2) {
-  MmParams p = {};
-  p.fmap1 = fmap1; p.fmap2[0] = fmap2; p.offset[0] = offset; p.coords = coords; p.corr = corr;
-  p.H2[0] = H2; p.W2[0] = W2;
-  p.L = 1; p.B = B; p.S = S; p.H1 = H1; p.W1 = W1;
-  p.lvl0 = 0; p.Ltot = 1;
-  return p;
-}
-int lowmem_mfma_dispatch(const _Float16* fmap1, const _Float16* fmap2, const float* coords, float* offset, float* corr,
-                         int B, int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
-  return mfma_dispatch<_Float16>(single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2), C, radius, st);
-}
-int lowmem_mfma_dispatch_f32(const float* fmap1, const float* fmap2, const float* coords, float* offset, float* corr,
-                             int B, int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
-  return mfma_dispatch<float>(single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2), C, radius, st);
-}
+int lowmem_mfma_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) { return mfma_dispatch<_Float16>(p, C, radius, st); }
+int lowmem_mfma_dispatch_f32(const LowmemParams& p, int C, int radius, hipStream_t st) { return mfma_dispatch<float>(p, C, radius, st); }
 
 }  // namespace lgu
 
@@ -640,23 +566,18 @@ static int pyramid_entry(bool half, const void* fmap1, const void* const* fmap2,
                          const int* orow = nullptr) {
   using namespace lgu;
   if (orow && (S != 1 || NO < 1)) return LGU_E_BADARG;
-  if (!fmap1 || !fmap2 || !coords || !offsets || !out || !H2 || !W2) return LGU_E_BADARG;
-  if (L < 1 || L > MM_MAXL || lbase < 0 || lbase > 16 || B < 0 || S < 1 || H1 < 1 || W1 < 1 || C < 1 || radius < 0)
-    return LGU_E_BADARG;
-  if ((long long)(B - 1) * (S - 1) >= (long long)NO || (ii == nullptr) != (jj == nullptr)) return LGU_E_BADARG;
-  MmParams p = {};
-  p.orow = orow; p.n_orow = NO;
-  p.fmap1 = fmap1;
-  for (int l = 0; l < L; l++) {
-    if (!fmap2[l] || H2[l] < 1 || W2[l] < 1) return LGU_E_BADARG;
-    p.fmap2[l] = fmap2[l];
-    p.offset[l] = offsets[l];
-    p.H2[l] = H2[l]; p.W2[l] = W2[l];
+  if (!fmap2 || !offsets || !H2 || !W2 || L < 1 || L > LOWMEM_MAXL || lbase < 0 || lbase > 16) return LGU_E_BADARG;
+  if ((ii == nullptr) != (jj == nullptr)) return LGU_E_BADARG;
+  const int rc0 = lowmem_entry_args({fmap1, coords, out, fmap2[0]}, B, S, H1, W1, H2, W2, L, C, radius, NO);
+  if (rc0 != LGU_OK) return rc0;
+  LowmemParams p = single_level(fmap1, fmap2[0], coords, offsets[0], out, B, S, H1, W1, H2[0], W2[0]);
+  for (int l = 1; l < L; l++) {
+    if (!fmap2[l]) return LGU_E_BADARG;
+    p.fmap2[l] = fmap2[l]; p.offset[l] = offsets[l]; p.H2[l] = H2[l]; p.W2[l] = W2[l];
   }
-  p.coords = coords; p.corr = out;
-  p.L = L; p.B = B; p.S = S; p.H1 = H1; p.W1 = W1;
+  p.L = p.Ltot = L;
   p.lbase = lbase; p.ii = ii; p.jj = jj;
-  p.lvl0 = 0; p.Ltot = L;
+  p.orow = orow; p.n_orow = NO;
   p.f2_chunked = chunked ? 1 : 0;
   if (B == 0) return LGU_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -709,7 +630,7 @@ extern "C" {
 int lgu_mm_diag_set_stamps(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(lgu::g_mm_stamps), &p, sizeof(p)); }
 int lgu_mm_diag_lowmem(const void* fmap1, const void* fmap2, const float* coords, float* offset, float* corr, int B, int S,
                        int H1, int W1, int H2, int W2, int C, int radius, int chunked, void* stream) {
-  lgu::MmParams p = lgu::single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2);
+  lgu::LowmemParams p = lgu::single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2);
   p.f2_chunked = chunked;
   return lgu::mfma_dispatch<_Float16>(p, C, radius, reinterpret_cast<hipStream_t>(stream));
 }

@@ -27,7 +27,7 @@
 // of pre-blended values: equal to fp32 rounding (tests: 1e-5).
 #include <type_traits>
 
-#include "lgu_common.hpp"
+#include "lowmem_family.hpp"
 
 namespace lgu {
 
@@ -54,10 +54,9 @@ __device__ __forceinline__ float piece_dot<float>(const float4& f, const float4&
   s = __builtin_fmaf(f.z, a.z, s); s = __builtin_fmaf(f.w, a.w, s);
   return s;
 }
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 template <>
 __device__ __forceinline__ float piece_dot<_Float16>(const float4& f, const float4& a, float s) {
-  const half8_t fh = __builtin_bit_cast(half8_t, f), ah = __builtin_bit_cast(half8_t, a);
+  const f16x8 fh = __builtin_bit_cast(f16x8, f), ah = __builtin_bit_cast(f16x8, a);
 #pragma unroll
   for (int i = 0; i < 8; i++) s = __builtin_fmaf((float)fh[i], (float)ah[i], s);  // channel order, fp32 accumulate
   return s;
@@ -331,53 +330,41 @@ __global__ __launch_bounds__(LT_WAVES * kWave) void lowmem_tile_kernel(const T* 
 }
 
 template <int R, typename T>
-static int launch_tile(const T* fmap1, const T* fmap2, const float* coords, float* offset, float* corr, int B, int S,
-                       int H1, int W1, int H2, int W2, int C, hipStream_t st) {
+static int launch_tile(const LowmemParams& p, int C, hipStream_t st) {
   const size_t lds = sizeof(float) * ((size_t)LT_STAGE_FLOATS + LT_PIX * 4 + 8 + LT_PIX * LT_CH * LT_SCMAX);
   auto kern = lowmem_tile_kernel<R, T>;
   allow_max_dynamic_lds<&lowmem_tile_kernel<R, T>>();
-  const int tiles_x = (W1 + LT_W - 1) / LT_W, tiles_y = (H1 + LT_H - 1) / LT_H;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)B * tiles_x * tiles_y), (unsigned)S), dim3(LT_WAVES * kWave), lds, st,
-                     fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, tiles_x, tiles_y);
+  const int tiles_x = (p.W1 + LT_W - 1) / LT_W, tiles_y = (p.H1 + LT_H - 1) / LT_H;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((size_t)p.B * tiles_x * tiles_y), (unsigned)p.S), dim3(LT_WAVES * kWave), lds, st,
+                     static_cast<const T*>(p.fmap1), static_cast<const T*>(p.fmap2[0]), p.coords, p.offset[0], p.corr, p.B, p.S,
+                     p.H1, p.W1, p.H2[0], p.W2[0], C, tiles_x, tiles_y);
   return launch_status();
 }
 
+// Single-level blocks only.  Returns -1 when this kernel does not serve the block.
 template <typename T>
-static int tile_dispatch(const T* fmap1, const T* fmap2, const float* coords, float* offset, float* corr, int B, int S,
-                         int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
-  // 16-byte channel loads of the maps; coords and offset (may be null) are read and written as 8-byte (x, y) pairs
-  const bool aligned = ((reinterpret_cast<uintptr_t>(fmap1) | reinterpret_cast<uintptr_t>(fmap2)) & 15) == 0 &&
-                       ((reinterpret_cast<uintptr_t>(coords) | reinterpret_cast<uintptr_t>(offset)) & 7) == 0;
+static int tile_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) {
   constexpr int epp = 16 / (int)sizeof(T);
-  if (radius < 1 || radius > 3 || C % (2 * epp) != 0 || !aligned || S > 65535) return -1;
-  if ((size_t)H2 * W2 * C >= (1u << 31) || (size_t)H1 * W1 * C >= (1u << 31)) return -1;  // 32-bit offsets inside one edge
+  if (p.L != 1 || !lowmem_tiled_serves(p, C, radius) || C % (2 * epp) != 0) return -1;
   switch (radius) {
-    case 1: return launch_tile<1, T>(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, st);
-    case 2: return launch_tile<2, T>(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, st);
-    default: return launch_tile<3, T>(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, st);
+    case 1: return launch_tile<1, T>(p, C, st);
+    case 2: return launch_tile<2, T>(p, C, st);
+    default: return launch_tile<3, T>(p, C, st);
   }
 }
 
-// Called from lgu_lowmem_defsample_fwd_f32 / lgu_altcorr_fwd_f32 (lowmem.hip).  Returns -1 when this
-// kernel does not serve the arguments (the caller then uses the wave-per-pixel kernel).
-int lowmem_tile_dispatch(const float* fmap1, const float* fmap2, const float* coords, float* offset, float* corr, int B,
-                         int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
-  return tile_dispatch<float>(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, radius, st);
-}
+// Called from lgu_lowmem_defsample_fwd_f32 / lgu_altcorr_fwd_f32 (lowmem.hip): -1 sends the caller to the wave-per-pixel kernel.
+int lowmem_tile_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) { return tile_dispatch<float>(p, C, radius, st); }
 
-// lowmem_mfma.hip
-int lowmem_mfma_dispatch(const _Float16* fmap1, const _Float16* fmap2, const float* coords, float* offset, float* corr,
-                         int B, int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st);
-
-// Half feature maps: the matrix-core kernel when it serves the shape, else the VALU tile kernel above.
+// Half feature maps: the matrix-core kernels when they serve the block, else the VALU tile kernel above.
 // LGU_LOWMEM_H16_VARIANT (debug/A-B only): 0 = matrix-core kernel, 1 = VALU tile kernel.
-static int h16_dispatch(const _Float16* fmap1, const _Float16* fmap2, const float* coords, float* offset, float* corr,
-                        int B, int S, int H1, int W1, int H2, int W2, int C, int radius, hipStream_t st) {
+static int h16_dispatch(const LowmemParams& p, int C, int radius, hipStream_t st) {
   if (env_int("LGU_LOWMEM_H16_VARIANT", 0) == 0) {
-    const int rc = lowmem_mfma_dispatch(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, radius, st);
+    const int rc = lowmem_mfma_dispatch(p, C, radius, st);
     if (rc >= 0) return rc;
   }
-  return tile_dispatch<_Float16>(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2, C, radius, st);
+  const int rc = tile_dispatch<_Float16>(p, C, radius, st);
+  return rc < 0 ? LGU_E_UNSUPPORTED : rc;
 }
 
 }  // namespace lgu
@@ -390,23 +377,20 @@ extern "C" {
 // feature maps stored in half precision, as droid_slam/depth_video.py keeps them.
 int lgu_lowmem_defsample_fwd_h16(const void* fmap1, const void* fmap2, const float* coords, float* offset, float* corr,
                                  int B, int S, int H1, int W1, int H2, int W2, int C, int NO, int radius, void* stream) {
-  if (!fmap1 || !fmap2 || !coords || !offset || !corr) return LGU_E_BADARG;
-  if (B < 0 || S < 1 || H1 < 1 || W1 < 1 || H2 < 1 || W2 < 1 || C < 1 || radius < 0) return LGU_E_BADARG;
-  if ((long long)(B - 1) * (S - 1) >= (long long)NO) return LGU_E_BADARG;
-  if (B == 0) return LGU_OK;
-  const int rc = lgu::h16_dispatch(static_cast<const _Float16*>(fmap1), static_cast<const _Float16*>(fmap2), coords,
-                                   offset, corr, B, S, H1, W1, H2, W2, C, radius, reinterpret_cast<hipStream_t>(stream));
-  return rc < 0 ? LGU_E_UNSUPPORTED : rc;
+  using namespace lgu;
+  const int rc = lowmem_entry_args({fmap1, fmap2, coords, offset, corr}, B, S, H1, W1, &H2, &W2, 1, C, radius, NO);
+  if (rc != LGU_OK || B == 0) return rc;
+  return h16_dispatch(single_level(fmap1, fmap2, coords, offset, corr, B, S, H1, W1, H2, W2), C, radius,
+                      reinterpret_cast<hipStream_t>(stream));
 }
 
 int lgu_altcorr_fwd_h16(const void* fmap1, const void* fmap2, const float* coords, float* corr, int B, int S, int H1,
                         int W1, int H2, int W2, int C, int radius, void* stream) {
-  if (!fmap1 || !fmap2 || !coords || !corr) return LGU_E_BADARG;
-  if (B < 0 || S < 1 || H1 < 1 || W1 < 1 || H2 < 1 || W2 < 1 || C < 1 || radius < 0) return LGU_E_BADARG;
-  if (B == 0) return LGU_OK;
-  const int rc = lgu::h16_dispatch(static_cast<const _Float16*>(fmap1), static_cast<const _Float16*>(fmap2), coords,
-                                   nullptr, corr, B, S, H1, W1, H2, W2, C, radius, reinterpret_cast<hipStream_t>(stream));
-  return rc < 0 ? LGU_E_UNSUPPORTED : rc;
+  using namespace lgu;
+  const int rc = lowmem_entry_args({fmap1, fmap2, coords, corr}, B, S, H1, W1, &H2, &W2, 1, C, radius, kAnyOffsetRows);
+  if (rc != LGU_OK || B == 0) return rc;
+  return h16_dispatch(single_level(fmap1, fmap2, coords, nullptr, corr, B, S, H1, W1, H2, W2), C, radius,
+                      reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

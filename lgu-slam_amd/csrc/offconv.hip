@@ -30,16 +30,13 @@ constexpr int OC_CHUNK = 2 * OC_NT * 1024;    // bytes of weight fragments per K
 constexpr int OC_WAVES = 4;                   // waves per workgroup
 constexpr int OC_RING = 3;                    // LDS ring of weight chunks: chunk s + 2 streams in while chunk s is multiplied
 
-typedef _Float16 oc_half8 __attribute__((ext_vector_type(8)));
-typedef float oc_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned oc_u32x4 __attribute__((ext_vector_type(4)));   // a fragment as the four dwords it is loaded as
 typedef __attribute__((address_space(3))) void oc_lds_void;
 typedef const __attribute__((address_space(1))) void oc_glb_void;
 
 // 16 bytes of zeros in device memory: what a tap outside the image loads (the select is on the ADDRESS, so the loaded
 // fragment is used as it arrives and no wait sits next to the load)
 // (16 fragments: the small-grid kernel adds a K-step offset of up to 12 fragments to whichever pointer the select produced)
-__device__ oc_u32x4 g_oc_zero[16] = {};  // not const: keeps it in the global address space (a constant-space pointer would turn the select into flat loads)
+__device__ u32x4 g_oc_zero[16] = {};  // not const: keeps it in the global address space (a constant-space pointer would turn the select into flat loads)
 
 struct OffConvParams {
   const _Float16* frames;  // (NF, H, W, C) channel-last, C = 128
@@ -111,11 +108,11 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_frames_kernel(const O
     px[t] = pc - py[t] * p.W;
   }
 
-  oc_f32x4 acc[MT][OC_NT];
+  f32x4 acc[MT][OC_NT];
 #pragma unroll
   for (int t = 0; t < MT; t++)
 #pragma unroll
-    for (int n = 0; n < OC_NT; n++) acc[t][n] = oc_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < OC_NT; n++) acc[t][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int nsteps = 9 * p.KS;
   // weight chunk `s` -> ring slot s % 3: 14 KiB = 3.5 x (256 threads x 16 bytes), contiguous in wpack
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_frames_kernel(const O
     }
   };
   // pixel fragments of step s: always loaded — taps outside the image read the zero fragment
-  auto load_a = [&](int s, oc_u32x4 (&a)[MT], oc_u32x4 (&al)[MT]) {
+  auto load_a = [&](int s, u32x4 (&a)[MT], u32x4 (&al)[MT]) {
     const int tap = s / p.KS, ks = s - tap * p.KS;
     const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
     const size_t fo = (ks < ksh ? o1 : o2) + (ks < ksh ? ks : ks - ksh) * 32 + kg * 8;
@@ -143,19 +140,19 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_frames_kernel(const O
       const int yy = py[t] + dy, xx = px[t] + dx;
       const bool ok = pv[t] && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W;
       const size_t off = fo + ((size_t)(ok ? yy : 0) * p.W + (ok ? xx : 0)) * p.C;
-      a[t] = *(ok ? reinterpret_cast<const oc_u32x4*>(p.frames + off) : g_oc_zero);
-      if (LO) al[t] = *(ok ? reinterpret_cast<const oc_u32x4*>(p.frames_lo + off) : g_oc_zero);
+      a[t] = *(ok ? reinterpret_cast<const u32x4*>(p.frames + off) : g_oc_zero);
+      if (LO) al[t] = *(ok ? reinterpret_cast<const u32x4*>(p.frames_lo + off) : g_oc_zero);
     }
   };
 
   // three register sets in fixed roles (step s uses set s % 3): no copies between them — a copy would have to wait for
   // the youngest load, i.e. drain the DMA queue behind it
-  oc_u32x4 ar[OC_RING][MT], lr_[OC_RING][MT];
+  u32x4 ar[OC_RING][MT], lr_[OC_RING][MT];
   stage(0, 0);
   load_a(0, ar[0], lr_[0]);
   stage(1, 1);
   load_a(1, ar[1], lr_[1]);
-  auto step = [&](int s, int slot, oc_u32x4 (&a)[MT], oc_u32x4 (&al)[MT], oc_u32x4 (&an)[MT], oc_u32x4 (&aln)[MT]) __attribute__((always_inline)) {
+  auto step = [&](int s, int slot, u32x4 (&a)[MT], u32x4 (&al)[MT], u32x4 (&an)[MT], u32x4 (&aln)[MT]) __attribute__((always_inline)) {
     // chunk s has landed (this wave's part): everything older than the DMA of chunk s + 1 and the pixel loads of
     // step s + 1 is complete when at most that many operations are outstanding (loads return in order)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + MT * (LO ? 2 : 1)) : "memory");
@@ -167,15 +164,15 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_frames_kernel(const O
     const char* const wb = wbuf + slot * OC_CHUNK + lane * 16;
 #pragma unroll
     for (int n = 0; n < OC_NT; n++) {
-      const oc_half8 bh = *reinterpret_cast<const oc_half8*>(wb + n * 1024);
-      const oc_half8 bl = *reinterpret_cast<const oc_half8*>(wb + (OC_NT + n) * 1024);
+      const f16x8 bh = *reinterpret_cast<const f16x8*>(wb + n * 1024);
+      const f16x8 bl = *reinterpret_cast<const f16x8*>(wb + (OC_NT + n) * 1024);
 #pragma unroll
       for (int t = 0; t < MT; t++) {
-        const oc_half8 av = __builtin_bit_cast(oc_half8, a[t]);
+        const f16x8 av = __builtin_bit_cast(f16x8, a[t]);
         acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bh, acc[t][n], 0, 0, 0);
         acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bl, acc[t][n], 0, 0, 0);
         if (LO) {
-          const oc_half8 alv = __builtin_bit_cast(oc_half8, al[t]);
+          const f16x8 alv = __builtin_bit_cast(f16x8, al[t]);
           acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alv, bh, acc[t][n], 0, 0, 0);
           acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alv, bl, acc[t][n], 0, 0, 0);
         }
@@ -205,7 +202,7 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_frames_kernel(const O
       if (ch >= p.Cout || pix0 >= HW) continue;
       const float b = bias ? bias[ch] : 0.f;
       float* dst = outp + ((size_t)e * p.Cout + ch) * HW + pix0;
-      const oc_f32x4 v = acc[t][n];
+      const f32x4 v = acc[t][n];
       if (pix0 + 3 < HW && (HW & 3) == 0) {
         *reinterpret_cast<float4*>(dst) = make_float4(v[0] + b, v[1] + b, v[2] + b, v[3] + b);
       } else {
@@ -254,9 +251,9 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_small_kernel(const Of
   const int pc = pv ? pix : HW - 1;
   const int py = pc / p.W, px = pc - py * p.W;
 
-  oc_f32x4 acc[OC_NTS];
+  f32x4 acc[OC_NTS];
 #pragma unroll
-  for (int n = 0; n < OC_NTS; n++) acc[n] = oc_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int n = 0; n < OC_NTS; n++) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // this wave's weight fragment of a chunk (a tile past the last one — odd tile count — re-reads the last tile into an LDS
   // position whose products are never stored)
@@ -316,13 +313,13 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_small_kernel(const Of
       if (k == 0) OC_STAGE(RING - 1, s2, cur, KS - 1)
       else OC_STAGE(k - 1, s2, nxt, k - 1)
       const char* const wb = wbuf + k * CHUNK + lane * 16;
-      const oc_half8 av = *reinterpret_cast<const oc_half8*>(adst + k * ASLOT + lane * 16);
-      oc_half8 alv;
-      if (LO) alv = *reinterpret_cast<const oc_half8*>(adst + k * ASLOT + 1024 + lane * 16);
+      const f16x8 av = *reinterpret_cast<const f16x8*>(adst + k * ASLOT + lane * 16);
+      f16x8 alv;
+      if (LO) alv = *reinterpret_cast<const f16x8*>(adst + k * ASLOT + 1024 + lane * 16);
 #pragma unroll
       for (int n = 0; n < OC_NTS; n++) {
-        const oc_half8 bh = *reinterpret_cast<const oc_half8*>(wb + n * 1024);
-        const oc_half8 bl = *reinterpret_cast<const oc_half8*>(wb + (OC_NTS + n) * 1024);
+        const f16x8 bh = *reinterpret_cast<const f16x8*>(wb + n * 1024);
+        const f16x8 bl = *reinterpret_cast<const f16x8*>(wb + (OC_NTS + n) * 1024);
         acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bh, acc[n], 0, 0, 0);
         acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bl, acc[n], 0, 0, 0);
         if (LO) {
@@ -344,7 +341,7 @@ __global__ __launch_bounds__(OC_WAVES* kWave) void offconv_small_kernel(const Of
     if (n0 + n >= OC_NT || ch >= p.Cout || pix0 >= HW) continue;
     const float b = p.bias ? p.bias[ch] : 0.f;
     float* dst = p.out + ((size_t)e * p.Cout + ch) * HW + pix0;
-    const oc_f32x4 v = acc[n];
+    const f32x4 v = acc[n];
     if (pix0 + 3 < HW && (HW & 3) == 0) {
       *reinterpret_cast<float4*>(dst) = make_float4(v[0] + b, v[1] + b, v[2] + b, v[3] + b);
     } else {

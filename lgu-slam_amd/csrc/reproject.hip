@@ -26,8 +26,6 @@ constexpr int RP_THREADS = 256;
 
 __device__ __forceinline__ bool edge_index_ok(long long v, int nvalid) { return v >= 0 && v < nvalid; }
 
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
 
 // NaN-propagating clamp (torch.clamp): a NaN fails both comparisons and is returned as it is.
 __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -79,16 +77,16 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_kernel(
       coords[pix * 3 + 1] = nan;
       coords[pix * 3 + 2] = nan;
     } else {
-      *reinterpret_cast<float2v*>(coords + pix * 2) = float2v{nan, nan};
+      *reinterpret_cast<f32x2*>(coords + pix * 2) = f32x2{nan, nan};
     }
     if (valid) valid[pix] = 0.0f;
     if (JAC) {
-      const float4v n4 = {nan, nan, nan, nan};
-      float4v* I4 = reinterpret_cast<float4v*>(Ji + pix * 12);
-      float4v* J4 = reinterpret_cast<float4v*>(Jj + pix * 12);
+      const f32x4 n4 = {nan, nan, nan, nan};
+      f32x4* I4 = reinterpret_cast<f32x4*>(Ji + pix * 12);
+      f32x4* J4 = reinterpret_cast<f32x4*>(Jj + pix * 12);
       I4[0] = n4; I4[1] = n4; I4[2] = n4;
       J4[0] = n4; J4[1] = n4; J4[2] = n4;
-      *reinterpret_cast<float2v*>(Jz + pix * 2) = float2v{nan, nan};
+      *reinterpret_cast<f32x2*>(Jz + pix * 2) = f32x2{nan, nan};
     }
     if (MOTN) {
       float* M = motn + ((size_t)b * num + e) * 4 * HW + k;
@@ -119,7 +117,7 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_kernel(
     coords[pix * 3 + 1] = cv;
     coords[pix * 3 + 2] = D * d;
   } else {
-    *reinterpret_cast<float2v*>(coords + pix * 2) = float2v{cu, cv};
+    *reinterpret_cast<f32x2*>(coords + pix * 2) = f32x2{cu, cv};
   }
   if (JAC) {
     const float a0 = fxj * d, a2 = ((-fxj * X1[0]) * d) * d;
@@ -148,18 +146,18 @@ __global__ __launch_bounds__(RP_THREADS) void reproject_kernel(
     cross3(r1, t, w);
     rt[0] = r1[3] + w[0]; rt[1] = r1[4] + w[1]; rt[2] = r1[5] + w[2];
     act_so3(qc, rt, s1 + 3);
-    float4v* J4 = reinterpret_cast<float4v*>(Jj + pix * 12);
-    J4[0] = float4v{r0[0], r0[1], r0[2], r0[3]};
-    J4[1] = float4v{r0[4], r0[5], r1[0], r1[1]};
-    J4[2] = float4v{r1[2], r1[3], r1[4], r1[5]};
-    float4v* I4 = reinterpret_cast<float4v*>(Ji + pix * 12);
-    I4[0] = float4v{-s0[0], -s0[1], -s0[2], -s0[3]};
-    I4[1] = float4v{-s0[4], -s0[5], -s1[0], -s1[1]};
-    I4[2] = float4v{-s1[2], -s1[3], -s1[4], -s1[5]};
-    *reinterpret_cast<float2v*>(Jz + pix * 2) = float2v{a0 * t[0] + a2 * t[2], b1 * t[1] + b2 * t[2]};
+    f32x4* J4 = reinterpret_cast<f32x4*>(Jj + pix * 12);
+    J4[0] = f32x4{r0[0], r0[1], r0[2], r0[3]};
+    J4[1] = f32x4{r0[4], r0[5], r1[0], r1[1]};
+    J4[2] = f32x4{r1[2], r1[3], r1[4], r1[5]};
+    f32x4* I4 = reinterpret_cast<f32x4*>(Ji + pix * 12);
+    I4[0] = f32x4{-s0[0], -s0[1], -s0[2], -s0[3]};
+    I4[1] = f32x4{-s0[4], -s0[5], -s1[0], -s1[1]};
+    I4[2] = f32x4{-s1[2], -s1[3], -s1[4], -s1[5]};
+    *reinterpret_cast<f32x2*>(Jz + pix * 2) = f32x2{a0 * t[0] + a2 * t[2], b1 * t[1] + b2 * t[2]};
   }
   if (MOTN) {
-    const float2v tg = *reinterpret_cast<const float2v*>(target + pix * 2);
+    const f32x2 tg = *reinterpret_cast<const f32x2*>(target + pix * 2);
     float* M = motn + ((size_t)b * num + e) * 4 * HW + k;
     M[0] = clamp_nan(cu - u, -bound, bound);
     M[HW] = clamp_nan(cv - v, -bound, bound);

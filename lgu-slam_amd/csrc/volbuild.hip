@@ -26,9 +26,6 @@
 
 namespace lgu {
 
-typedef float vbf32x16 __attribute__((ext_vector_type(16)));
-typedef float vbf32x4 __attribute__((ext_vector_type(4)));   // (HIP's float4 struct in a loop-carried array stays on the stack)
-typedef _Float16 vbh8 __attribute__((ext_vector_type(8)));
 
 constexpr int VB_M = 32;        // source pixels per workgroup
 constexpr int VB_ROWS = 8;      // target rows per strip
@@ -100,7 +97,7 @@ __global__ __launch_bounds__(VB_THREADS, 2) void volume_build_kernel(const VolBu
   // (rows of the NCHW maps are contiguous in the positions) into registers WHILE the matrix cores work on the chunk that is in
   // LDS; operands are then single ds_read_b32s (lane = position, the k slot selects the row).  The chunk buffers share LDS
   // with the epilogue's staging area (used after the last chunk).
-  vbf32x16 acc[NTW];
+  f32x16 acc[NTW];
 #pragma unroll
   for (int t = 0; t < NTW; t++)
 #pragma unroll
@@ -115,13 +112,13 @@ __global__ __launch_bounds__(VB_THREADS, 2) void volume_build_kernel(const VolBu
     // long as the whole epilogue: 0.21 of 0.42 ms at 20 edges.)  Per 32-channel chunk: 2 loads per tile, the next chunk's
     // travelling under this chunk's MFMAs.  The maps are L2-resident (0.75 MB per edge).
     const int S = p.C >> 4, T = HW / 32;
-    const vbh8* const fa = reinterpret_cast<const vbh8*>(p.th);
+    const f16x8* const fa = reinterpret_cast<const f16x8*>(p.th);
     // (16-byte units; the host checks that the packed maps hold fewer than 2^32 of them)
     const unsigned abase = ((unsigned)(e * 2 + 0) * T + mb) * S * 64 + lane;
     unsigned bbase[NTW];
 #pragma unroll
     for (int t = 0; t < NTW; t++) bbase[t] = ((unsigned)(e * 2 + 1) * T + s * (N / 32) + wv * NTW + t) * S * 64 + lane;
-    vbh8 a[2], b[NTW][2], na[2], nb[NTW][2];
+    f16x8 a[2], b[NTW][2], na[2], nb[NTW][2];
 #define VB_FETCH_H(s0)                                                                          \
   {                                                                                             \
     na[0] = fa[abase + (unsigned)(s0) * 64u];                                                   \
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(VB_THREADS, 2) void volume_build_kernel(const VolBu
     const float* const f1e = p.f1 + mapbase + mb * VB_M;
     const float* const f2e = p.f2 + mapbase + s * N;
     const int tid = threadIdx.x;
-    vbf32x4 gb[BQ], ga;
+    f32x4 gb[BQ], ga;
     // this thread's share of a chunk: BQ float4s of the target rows, one of the source rows (threads 0 .. 127)
     int brow[BQ], bc4[BQ];
 #pragma unroll
@@ -167,16 +164,16 @@ __global__ __launch_bounds__(VB_THREADS, 2) void volume_build_kernel(const VolBu
 #define VB_FETCH(c0)                                                                                              \
   {                                                                                                               \
     _Pragma("unroll") for (int j = 0; j < BQ; j++)                                                                \
-        gb[j] = *reinterpret_cast<const vbf32x4*>(f2e + (size_t)((c0) + brow[j]) * HW + bc4[j]);                   \
-    ga = *reinterpret_cast<const vbf32x4*>(f1e + (size_t)((c0) + arow) * HW + ac4);                                \
+        gb[j] = *reinterpret_cast<const f32x4*>(f2e + (size_t)((c0) + brow[j]) * HW + bc4[j]);                     \
+    ga = *reinterpret_cast<const f32x4*>(f1e + (size_t)((c0) + arow) * HW + ac4);                                  \
   }
     const int kk = lane >> 5, li = lane & 31;                   // operand lane: k slot, row / column
     VB_FETCH(0)
     for (int c0 = 0; c0 < p.C; c0 += VB_KC) {
       __syncthreads();                                           // the chunk in LDS has been consumed
 #pragma unroll
-      for (int j = 0; j < BQ; j++) reinterpret_cast<vbf32x4*>(Bs)[tid + VB_THREADS * j] = gb[j];
-      if (tid < VB_KC * VB_M / 4) reinterpret_cast<vbf32x4*>(As)[tid] = ga;
+      for (int j = 0; j < BQ; j++) reinterpret_cast<f32x4*>(Bs)[tid + VB_THREADS * j] = gb[j];
+      if (tid < VB_KC * VB_M / 4) reinterpret_cast<f32x4*>(As)[tid] = ga;
       __syncthreads();
       {
         const int cn = c0 + VB_KC < p.C ? c0 + VB_KC : c0;       // (after the last chunk: the same one again, unused)
@@ -327,7 +324,7 @@ __global__ __launch_bounds__(256) void volume_pack_kernel(const _Float16* __rest
   const unsigned map = q & 1u, e = q >> 1;
   const unsigned h = lane >> 5, li = lane & 31u;
   const size_t src = ((size_t)e * HW + tile * 32u + li) * (size_t)(2 * C) + map * (unsigned)C + 16u * st + 8u * h;
-  reinterpret_cast<vbh8*>(packed)[o] = *reinterpret_cast<const vbh8*>(feats + src);
+  reinterpret_cast<f16x8*>(packed)[o] = *reinterpret_cast<const f16x8*>(feats + src);
 }
 
 template <int NTW, bool HALF>

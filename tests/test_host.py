@@ -459,6 +459,70 @@ def test_lowmem_plan_argument_checks(lgu):
         ops.LowmemPyramidPlan(h.float(), [h], [None], 3)
 
 
+def _lowmem_refusal_cases():
+    """(entry, base-call overrides, expected code) for the C entries of the on-the-fly family.  Every case is refused
+    before any HIP call, so fake (non-null, 64-byte aligned) addresses and a null stream are enough."""
+    OK, BAD, UNS = 0, 100001, 100002
+    single = [   # what every single-level entry refuses
+        (dict(fmap2=None), BAD), (dict(B=-1), BAD), (dict(S=0), BAD), (dict(H2=0), BAD), (dict(radius=-1), BAD),
+        (dict(B=0), OK), (dict(C=24), UNS)]
+    f32 = [(dict(radius=8), BAD)]   # LGU_MAX_RADIUS = 7
+    h16 = [(dict(radius=4), UNS), (dict(radius=0), UNS), (dict(fmap1="+2"), UNS), (dict(S=70000, NO=70000), UNS)]
+    rows = (dict(B=2, S=2, NO=1), BAD)
+    pyr = [(dict(L=5), BAD), (dict(radius=4), UNS), (dict(radius=0), UNS), (dict(C=48), UNS), (dict(jj=None), BAD),
+           (dict(H2=[4, 0]), BAD), (dict(B=0), OK), (dict(coords=None), BAD), (dict(lbase=17), BAD), (dict(B=2, S=2, NO=1), BAD)]
+    cases = {
+        "lgu_lowmem_defsample_fwd_h16": single + h16 + [rows, (dict(offset=None), BAD)],
+        "lgu_lowmem_defsample_fwd_f32": single + f32 + [rows, (dict(offset=None), BAD), (dict(C=24, offset=None), UNS)],
+        "lgu_altcorr_fwd_h16": single + h16,
+        "lgu_altcorr_fwd_f32": single + f32 + [(dict(radius=4), UNS)],
+        "lgu_altcorr_bwd_f32": single + f32 + [(dict(radius=4), UNS), (dict(fmap2_grad=None), BAD)],
+        "lgu_lowmem_pyramid_fwd_h16": pyr + [(dict(fmap1="+2"), UNS)],
+        "lgu_lowmem_pyramid_fwd_f32": pyr + [(dict(fmap1="+2"), UNS)],
+        "lgu_lowmem_pyramid_chunked_fwd_h16": pyr + [(dict(fmap1="+2"), UNS)],
+        "lgu_lowmem_pyramid_chunked_fwd_f32": pyr + [(dict(fmap1="+2"), UNS)],
+        "lgu_lowmem_pyramid_calls_fwd_h16": [c for c in pyr if "S" not in c[0]] + [(dict(off_row=None), BAD), (dict(NO=0), BAD)],
+    }
+    return [pytest.param(e, o, c, id="%s-%s" % (e[4:], ",".join("%s=%s" % kv for kv in o.items()))) for e, cs in cases.items() for o, c in cs]
+
+
+@pytest.mark.parametrize("entry,override,code", _lowmem_refusal_cases())
+def test_lowmem_entries_refuse_bad_arguments(lgu, entry, override, code):
+    """The codes the family's entries answer for arguments they refuse (include/lgu_corr.h): LGU_E_BADARG for null
+    pointers, non-positive sizes, too few offset rows and a radius above LGU_MAX_RADIUS; LGU_E_UNSUPPORTED for what no
+    kernel serves; LGU_OK for an empty call.  The entries differ on purpose: the float entries refuse C % 32 != 0 at
+    the door, the half ones when no kernel takes the call."""
+    import ctypes
+    lib = lgu._lib.load()
+    names = ["fmap1", "fmap2", "coords", "offset", "corr", "corr_grad", "fmap1_grad", "fmap2_grad", "out", "ii", "jj", "off_row"]
+    a = {n: 0x100000 * (i + 1) for i, n in enumerate(names)}   # fake addresses, 64-byte aligned
+    a.update(B=1, S=1, H1=4, W1=4, C=32, NO=1, radius=3, lbase=0, chunked=0)
+    pyramid = "pyramid" in entry
+    a.update(dict(L=2, H2=[4, 2], W2=[4, 2]) if pyramid else dict(H2=4, W2=4))
+    for k, v in override.items():
+        a[k] = a[k] + 2 if v == "+2" else v
+    if pyramid:
+        L = max(min(a["L"], 4), 1)
+        fmap2 = (ctypes.c_void_p * 4)(*[0x4000000 + 0x100000 * l for l in range(L)])
+        offsets = (ctypes.c_void_p * 4)(0x5000000)   # offsets on level 0 only
+        H2 = (ctypes.c_int * 4)(*(a["H2"] + [1] * 4)[:4])
+        W2 = (ctypes.c_int * 4)(*(a["W2"] + [1] * 4)[:4])
+        head = [a["fmap1"], fmap2, a["coords"], offsets, a["out"], a["L"], a["lbase"], a["B"]]
+        if "calls" in entry:
+            args = head + [a["H1"], a["W1"], H2, W2, a["C"], a["NO"], a["off_row"], a["radius"], a["ii"], a["jj"], a["chunked"], None]
+        else:
+            args = head + [a["S"], a["H1"], a["W1"], H2, W2, a["C"], a["NO"], a["radius"], a["ii"], a["jj"], None]
+    else:
+        dims = [a[k] for k in ("B", "S", "H1", "W1", "H2", "W2", "C")]
+        if "defsample" in entry:
+            args = [a["fmap1"], a["fmap2"], a["coords"], a["offset"], a["corr"]] + dims + [a["NO"], a["radius"], None]
+        elif "bwd" in entry:
+            args = [a["fmap1"], a["fmap2"], a["coords"], a["corr_grad"], a["fmap1_grad"], a["fmap2_grad"]] + dims + [a["radius"], None]
+        else:
+            args = [a["fmap1"], a["fmap2"], a["coords"], a["corr"]] + dims + [a["radius"], None]
+    assert getattr(lib, entry)(*args) == code
+
+
 def test_corr_encoder_host_logic():
     """CorrEncoder: structure check, and anything that is not a channel-last half CUDA tensor is handed to
     the wrapped module unchanged (the reference call, droid_net.py:116)."""
