@@ -732,6 +732,31 @@ long lgu_instnorm_resident_limit(int elem_bytes); /* largest hw served by the si
 int lgu_image_normalize_u8(const unsigned char* img, float* out, long n, long hw, const float mean[3], const float std[3],
                            void* stream);
 
+/* ---- motion (flow) encoder: the 7x7 first layer with its ReLU, under float16 autocast (csrc/flowenc.hip) -----------------
+ * Reference droid_slam/droid_net.py:82-84: flow_encoder = Conv2d(4, 128, 7, padding=3), ReLU(inplace=True), ... evaluated
+ * under the float16 autocast of the update operator.  x (N,4,H,W) float32 planar, what lgu_motion_features_f32 writes;
+ * out (N,128,H,W) IEEE half, NCHW contiguous, fully written and nothing outside it.  Rounding points:
+ *   x_h = half(x), w_h = half(weight), b_h = half(bias)     round to nearest even (x_h in the kernel, the others in the pack)
+ *   s   = b_h + sum over c, ky, kx of x_h * w_h             exact half x half products, fp32 accumulation, zero padding
+ *   y   = relu(half(s))                                     ONE rounding; relu keeps a NaN
+ * A NaN or infinite input reaches exactly the output pixels whose 7x7 window covers it.  No atomics, no workspace: the
+ * bits of an image depend on that image, H and W only, not on N or on its position in the batch.
+ * wpack: LGU_FLOW_CONV7_WPACK_HALVES halves laid out [7 window rows ky][8 channel tiles ct][64 lanes l][8 halves j], the B
+ *   operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is w_h[16 ct + (l & 15)][c][ky][kx] with
+ *   k = 8 (l >> 4) + j, kx = k / 4, c = k % 4, and zero where kx == 7 (the padding slot that makes a window row one K step
+ *   of 32).  16-byte aligned, otherwise LGU_E_UNSUPPORTED.  bias: 128 halves b_h.
+ * x, bias and out are served at the alignment of their element: out is stored 8 bytes at a time where W % 4 == 0 and out
+ *   is 8-byte aligned, by element otherwise, with the same arithmetic and the same bits.
+ * Every N >= 0, H >= 1, W >= 1 is served; N == 0 launches nothing.  N < 0, H < 1, W < 1, a null operand or one below its
+ * element's alignment: LGU_E_BADARG; more than INT_MAX workgroups (N * ceil(W / 64) * ceil(H / 8)): LGU_E_UNSUPPORTED.
+ * The operands travel in one parameter block passed by value. */
+#define LGU_FLOW_CONV7_WPACK_HALVES 28672
+typedef struct {
+  const float* x; const void* wpack; const void* bias; void* out;   /* bias: 128 halves */
+  int N, H, W;
+} lgu_flow_conv7_args;
+int lgu_flow_conv7_relu_h16(lgu_flow_conv7_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

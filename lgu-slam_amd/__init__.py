@@ -10,10 +10,11 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, encoder, features, geom, graph, gru, lie, ops, sharded  # noqa: F401
+from . import _build, _lib, aggregate, ba, encoder, features, flow, geom, graph, gru, lie, ops, sharded  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
+from .flow import FlowEncoder  # noqa: F401
 from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
 from .gru import KanBiasGRU  # noqa: F401
 

@@ -13,6 +13,12 @@ _c_float_p = ctypes.POINTER(ctypes.c_float)
 _vp = ctypes.c_void_p
 _int = ctypes.c_int
 
+
+class FlowConv7Args(ctypes.Structure):
+    """lgu_flow_conv7_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int)]
+
+
 # name -> argument types (return type is always int)
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -123,6 +129,8 @@ SIGNATURES = {
     "lgu_instnorm_resident_limit": [_int],   # elem_bytes; returns long (set in load())
     # img, out, n, hw, mean[3], std[3], stream
     "lgu_image_normalize_u8": [_vp, _vp, ctypes.c_long, ctypes.c_long, _c_float_p, _c_float_p, _vp],
+    # motion encoder: {x, wpack, bias, out, N, H, W} by value, stream
+    "lgu_flow_conv7_relu_h16": [FlowConv7Args, _vp],
 }
 
 _lib = None
