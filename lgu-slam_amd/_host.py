@@ -1,0 +1,191 @@
+"""The host vocabulary of the operator layer, once: pointer and stream plumbing, the dtype names, the argument refusals,
+the launch, and what the module wrappers (FeatureEncoder, KanBiasGRU, FlowEncoder, ProximityFactors) share.
+
+Every refusal takes a list of (tensor, "name") pairs and raises the text the reference (or torch) raises for the same
+defect.  The ORDER in which an operator calls them is part of its behaviour (an argument with two defects reports the
+first): each operator states its own order, nothing here reorders checks across operators.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+_vp = ctypes.c_void_p
+
+
+# ---- pointers, streams, the device guard ----------------------------------------------------------------------------
+def ptr(t):
+    return _vp(t.data_ptr())
+
+
+def stream(t):
+    return _vp(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+class CurrentDevice:
+    """Launch guard: the library launches on the CURRENT device, so a call whose buffers live on another device switches
+    for the call — and costs one integer comparison when it already is current (the usual one-process-per-GPU case)."""
+
+    def __init__(self, device):
+        self.idx = device.index if device.index is not None else torch.cuda.current_device()
+        self.prev = -1
+
+    def __enter__(self):
+        cur = torch.cuda.current_device()
+        if cur != self.idx:
+            self.prev = cur
+            torch.cuda.set_device(self.idx)
+
+    def __exit__(self, *exc):
+        if self.prev >= 0:
+            torch.cuda.set_device(self.prev)
+            self.prev = -1
+        return False
+
+
+SUFFIX = {torch.float32: "_f32", torch.float16: "_h16"}     # lgu_<entry>_f32 / _h16 by tensor dtype
+FLOAT_OR_HALF = tuple(SUFFIX)
+
+
+def typed(symbol, dtype):
+    return symbol + SUFFIX[dtype]
+
+
+def launch(symbol, what, device, *args):
+    """One library call on `device`: a non-zero return code raises as "`what` failed: ..." (_lib.check)."""
+    with CurrentDevice(device):
+        rc = getattr(_lib.load(), symbol)(*args)
+    if rc:
+        _lib.check(rc, what)
+
+
+# ---- dtype names ----------------------------------------------------------------------------------------------------
+_TORCH_NAME = {torch.float32: "Float", torch.float16: "Half", torch.float64: "Double", torch.bfloat16: "BFloat16",
+               torch.int64: "Long", torch.int32: "Int"}
+
+
+def dtype_name(dt):
+    """The name torch's own "expected scalar type" errors use; a dtype outside the table as torch prints it."""
+    return _TORCH_NAME.get(dt, str(dt))
+
+
+def bare_name(dt):
+    """torch's spelling without the prefix ("float16"): what the correlation operators' refusals print."""
+    return str(dt).replace("torch.", "")
+
+
+# ---- refusals -------------------------------------------------------------------------------------------------------
+_CONTIGUOUS = "%s must be contiguous"
+_NO_CPU = "%s must be a HIP device tensor: lgu_slam_amd has no CPU fallback"
+
+
+def check_contiguous(pairs):
+    """The reference's CHECK_INPUT: TORCH_CHECK(x.is_contiguous(), #x " must be contiguous") (droid.cpp:48-49)."""
+    for t, name in pairs:
+        if not t.is_contiguous():
+            raise RuntimeError(_CONTIGUOUS % name)
+
+
+def check_dtype(pairs, want):
+    """Every tensor has dtype `want`, or one of them if `want` is a tuple ("Float or Half")."""
+    ok = want if isinstance(want, tuple) else (want,)
+    for t, name in pairs:
+        if t.dtype not in ok:
+            raise RuntimeError("expected scalar type %s but found %s (%s)"
+                               % (" or ".join(dtype_name(d) for d in ok), dtype_name(t.dtype), name))
+
+
+def check_same_dtype(pairs, first=FLOAT_OR_HALF):
+    """The first tensor's dtype is one of `first` and every other tensor has it; returns it."""
+    check_dtype(pairs[:1], first)
+    check_dtype(pairs[1:], pairs[0][0].dtype)
+    return pairs[0][0].dtype
+
+
+def check_shape(pairs, shape):
+    for t, name in pairs:
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+
+
+def check_hip(pairs):
+    for t, name in pairs:
+        if not t.is_cuda:
+            raise RuntimeError(_NO_CPU % name)
+
+
+def check_device(pairs):
+    """Every tensor on a HIP device, then every tensor on the first one's."""
+    check_hip(pairs)
+    for t, name in pairs:
+        if t.device != pairs[0][0].device:
+            raise RuntimeError("%s is on %s, expected %s" % (name, t.device, pairs[0][0].device))
+
+
+def needs_grad(tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def check_no_grad(what, pairs):
+    if needs_grad([t for t, _ in pairs]):
+        raise RuntimeError("%s has no autograd: its outputs would carry no gradient. Call it under torch.no_grad() or "
+                           "pass detached inputs" % what)
+
+
+def check_operands(pairs, dtype=None):
+    """The order of the correlation operators and of ba: CHECK_INPUT on every argument first, then per argument what this
+    library additionally requires, HIP device and dtype.  dtype None: float32, named "Float" as the reference's accessors
+    name it; a given dtype is printed bare.  (One call frame: the prepared plans call this once per lookup.)"""
+    for t, name in pairs:
+        if not t.is_contiguous():
+            raise RuntimeError(_CONTIGUOUS % name)
+    want, spelled = (torch.float32, "Float") if dtype is None else (dtype, bare_name(dtype))
+    for t, name in pairs:
+        if not t.is_cuda:
+            raise RuntimeError(_NO_CPU % name)
+        if t.dtype != want:
+            raise RuntimeError("expected scalar type %s but found %s (%s)" % (spelled, bare_name(t.dtype), name))
+
+
+# ---- what the module wrappers share ---------------------------------------------------------------------------------
+def is_conv(m, cin, cout, k, stride=1, pad=0, bias=None):
+    """m is Conv2d(cin, cout, k, stride, pad) without dilation, groups or a padding mode; bias=True: and has a bias."""
+    return (isinstance(m, torch.nn.Conv2d) and m.in_channels == cin and m.out_channels == cout and m.kernel_size == (k, k)
+            and m.stride == (stride, stride) and m.padding == (pad, pad) and m.dilation == (1, 1) and m.groups == 1
+            and m.padding_mode == "zeros" and (not bias or m.bias is not None))
+
+
+def param_key(tensors):
+    """Identity of the parameters a packed-weight cache was made of: load_state_dict, in-place updates and moves change it."""
+    return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+
+
+def fused_dtype(tensors):
+    """The dtype a fused path computes in now: float16 under CUDA float16 autocast, float32 with autocast off; None (the
+    module's own forward) under any other autocast, or when grad mode is on and one of `tensors` requires grad."""
+    if needs_grad(tensors):
+        return None
+    if torch.is_autocast_enabled("cuda"):
+        return torch.float16 if torch.get_autocast_dtype("cuda") == torch.float16 else None
+    return torch.float32
+
+
+def bind(obj, attr, cls, make):
+    """Set `make(previous instance attribute or None)` as the instance attribute obj.attr (the class and a module's
+    parameters, buffers and state_dict keys are untouched); a `cls` already bound there is returned instead."""
+    cur = obj.__dict__.get(attr)
+    if isinstance(cur, cls):
+        return cur
+    wrapper = make(cur)
+    setattr(obj, attr, wrapper)
+    return wrapper
+
+
+def unbind(obj, attr, cls):
+    """Undo `bind`: the class's attribute is used again.  Returns the wrapper that was removed, or None."""
+    cur = obj.__dict__.get(attr)
+    if isinstance(cur, cls):
+        delattr(obj, attr)
+        return cur
+    return None

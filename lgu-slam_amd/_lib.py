@@ -19,7 +19,7 @@ class FlowConv7Args(ctypes.Structure):
     _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int)]
 
 
-# name -> argument types (return type is always int)
+# name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
     "lgu_defcorr_bwd_f32": [_vp] * 6 + [_int] * 6 + [_vp],
@@ -126,12 +126,25 @@ SIGNATURES = {
     # feature encoder: a, b, out, planes, hw, eps, mode, stream
     "lgu_instnorm_relu_f32": [_vp] * 3 + [ctypes.c_long] * 2 + [ctypes.c_float, _int, _vp],
     "lgu_instnorm_relu_h16": [_vp] * 3 + [ctypes.c_long] * 2 + [ctypes.c_float, _int, _vp],
-    "lgu_instnorm_resident_limit": [_int],   # elem_bytes; returns long (set in load())
+    "lgu_instnorm_resident_limit": [_int],   # elem_bytes
     # img, out, n, hw, mean[3], std[3], stream
     "lgu_image_normalize_u8": [_vp, _vp, ctypes.c_long, ctypes.c_long, _c_float_p, _c_float_p, _vp],
     # motion encoder: {x, wpack, bias, out, N, H, W} by value, stream
     "lgu_flow_conv7_relu_h16": [FlowConv7Args, _vp],
+    # size queries (host only) and the library's own description
+    "lgu_ba_solve_blocked_work_doubles": [_int],
+    "lgu_offsets_finalize_scratch_bytes": [_int],
+    "lgu_proximity_prefix_len": [_int] * 4,
+    "lgu_proximity_capacity": [_int] * 5 + [ctypes.c_longlong],
+    "lgu_proximity_work_bytes": [_int] * 3,
+    "lgu_version": [],
+    "lgu_error_string": [_int],
+    "lgu_debug_knobs_enabled": [],
 }
+RESTYPES = {name: ctypes.c_longlong for name in (
+    "lgu_ba_solve_blocked_work_doubles", "lgu_offsets_finalize_scratch_bytes", "lgu_proximity_prefix_len", "lgu_proximity_capacity",
+    "lgu_proximity_work_bytes")}
+RESTYPES.update(lgu_instnorm_resident_limit=ctypes.c_long, lgu_version=ctypes.c_char_p, lgu_error_string=ctypes.c_char_p)
 
 _lib = None
 
@@ -170,21 +183,7 @@ def load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, let it surface
         fn.argtypes = argtypes
-        fn.restype = _int
-    lib.lgu_ba_solve_blocked_work_doubles.restype = ctypes.c_longlong
-    lib.lgu_ba_solve_blocked_work_doubles.argtypes = [_int]
-    lib.lgu_offsets_finalize_scratch_bytes.restype = ctypes.c_longlong
-    lib.lgu_offsets_finalize_scratch_bytes.argtypes = [_int]
-    for name, argtypes in (("lgu_proximity_prefix_len", [_int] * 4), ("lgu_proximity_capacity", [_int] * 5 + [ctypes.c_longlong]),
-                           ("lgu_proximity_work_bytes", [_int] * 3)):
-        getattr(lib, name).restype = ctypes.c_longlong
-        getattr(lib, name).argtypes = argtypes
-    lib.lgu_instnorm_resident_limit.restype = ctypes.c_long
-    lib.lgu_version.restype = ctypes.c_char_p
-    lib.lgu_debug_knobs_enabled.restype = _int
-    lib.lgu_debug_knobs_enabled.argtypes = []
-    lib.lgu_error_string.restype = ctypes.c_char_p
-    lib.lgu_error_string.argtypes = [_int]
+        fn.restype = RESTYPES.get(name, _int)
     _lib = lib
     return lib
 

@@ -16,27 +16,11 @@ on the current stream of the inputs' device, without host synchronisation (graph
 """
 import torch
 
-from . import _lib
-from .geom import _check_device, _check_no_grad
-from .ops import _TORCH_NAME, _ptr, _stream
+from ._host import FLOAT_OR_HALF, check_contiguous, check_device, check_dtype, check_no_grad, launch, typed
+from ._host import ptr as _ptr, stream as _stream
 
 UPS_MASK_F16, UPS_HALF_WEIGHTS = 1, 2     # include/lgu_corr.h LGU_UPS_*
 _MASK_CH = 8 * 8 * 9
-
-
-def _contiguous(*named):
-    for t, name in zip(named[0::2], named[1::2]):
-        if not t.is_contiguous():
-            raise RuntimeError("%s must be contiguous" % name)
-
-
-def _dtype_name(dt):
-    return _TORCH_NAME.get(dt, str(dt))
-
-
-def _index(t, name):
-    if t.dtype != torch.int64:
-        raise RuntimeError("expected scalar type Long but found %s (%s)" % (_dtype_name(t.dtype), name))
 
 
 def scatter_mean(src, index, dim=-1, out=None, dim_size=None):
@@ -59,14 +43,14 @@ def scatter_mean(src, index, dim=-1, out=None, dim_size=None):
     if index.dim() != 1 or index.shape[0] != src.shape[dim]:
         raise NotImplementedError("scatter_mean: only a 1-D index of length src.size(dim) = %d is supported (the "
                                   "reference's call form), got index of shape %s" % (src.shape[dim], tuple(index.shape)))
-    _contiguous(src, "src", index, "index")
-    if src.dtype not in (torch.float32, torch.float16):
-        raise RuntimeError("expected scalar type Float or Half but found %s (src)" % _dtype_name(src.dtype))
-    _index(index, "index")
+    named = [(src, "src"), (index, "index")]
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:], torch.int64)
     if dim_size is not None and int(dim_size) < 0:
         raise RuntimeError("dim_size must be >= 0, got %d" % int(dim_size))
-    _check_no_grad("scatter_mean", src)
-    _check_device([(src, "src"), (index, "index")])
+    check_no_grad("scatter_mean", named)
+    check_device(named)
     n = src.shape[dim]
     if dim_size is None:
         M = max(int(index.max()) + 1, 0) if n > 0 else 0     # host sync, as in torch_scatter; all negative: M = 0
@@ -83,20 +67,17 @@ def scatter_mean(src, index, dim=-1, out=None, dim_size=None):
     res = torch.empty(shape, dtype=src.dtype, device=src.device)
     if res.numel() == 0:
         return res
-    fn = "lgu_scatter_mean_f32" if src.dtype == torch.float32 else "lgu_scatter_mean_h16"
-    with torch.cuda.device(src.device):
-        rc = getattr(_lib.load(), fn)(_ptr(src), _ptr(index), outer, n, inner, M, _ptr(res), _stream(src))
-    _lib.check(rc, "scatter_mean")
+    launch(typed("lgu_scatter_mean", src.dtype), "scatter_mean", src.device, _ptr(src), _ptr(index), outer, n, inner, M, _ptr(res),
+           _stream(src))
     return res
 
 
 def _mask_flags(mask):
     """LGU_UPS_* for this mask as torch would compute the reference's softmax: a half mask gives half weights, unless
     autocast is on (softmax is on autocast's float32 list, the weights stay float32)."""
+    check_dtype([(mask, "mask")], FLOAT_OR_HALF)
     if mask.dtype == torch.float32:
         return 0
-    if mask.dtype != torch.float16:
-        raise RuntimeError("expected scalar type Float or Half but found %s (mask)" % _dtype_name(mask.dtype))
     return UPS_MASK_F16 | (0 if torch.is_autocast_enabled() else UPS_HALF_WEIGHTS)
 
 
@@ -110,11 +91,6 @@ def _check_mask(mask, U, ht, wd):
                            % (U, _MASK_CH, ht, wd, tuple(mask.shape)))
 
 
-def _check_float(t, name):
-    if t.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float but found %s (%s)" % (_dtype_name(t.dtype), name))
-
-
 def cvx_upsample(data, mask):
     """The reference's cvx_upsample (droid_net.py:15-29) for data width 1: data (B,ht,wd,1) float32, mask (B,576,ht,wd)
     (optionally with leading 1s) float32 or float16 -> (B,8ht,8wd,1) float32.  Each output is the
@@ -124,19 +100,19 @@ def cvx_upsample(data, mask):
         raise RuntimeError("data must be (B,ht,wd,dim), got %s" % (tuple(data.shape),))
     if data.shape[3] != 1:
         raise NotImplementedError("cvx_upsample: only data width 1 (the disparity) is supported, got %d" % data.shape[3])
-    _contiguous(data, "data", mask, "mask")
-    _check_float(data, "data")
+    named = [(data, "data"), (mask, "mask")]
+    check_contiguous(named)
+    check_dtype(named[:1], torch.float32)
     B, ht, wd, _ = data.shape
     _check_mask(mask, B, ht, wd)
     flags = _mask_flags(mask)
-    _check_no_grad("cvx_upsample", data, mask)
-    _check_device([(data, "data"), (mask, "mask")])
+    check_no_grad("cvx_upsample", named)
+    check_device(named)
     res = torch.empty((B, 8 * ht, 8 * wd, 1), dtype=torch.float32, device=data.device)
     if res.numel() == 0:
         return res
-    with torch.cuda.device(data.device):
-        rc = _lib.load().lgu_cvx_upsample_f32(_ptr(data), _ptr(mask), B, ht, wd, flags, _ptr(res), _stream(data))
-    _lib.check(rc, "cvx_upsample")
+    launch("lgu_cvx_upsample_f32", "cvx_upsample", data.device, _ptr(data), _ptr(mask), B, ht, wd, flags, _ptr(res),
+           _stream(data))
     return res
 
 
@@ -146,7 +122,7 @@ def upsample_disp(disp, mask):
     if disp.dim() != 4:
         raise RuntimeError("disp must be (batch,num,ht,wd), got %s" % (tuple(disp.shape),))
     batch, num, ht, wd = disp.shape
-    _contiguous(disp, "disp", mask, "mask")
+    check_contiguous([(disp, "disp"), (mask, "mask")])
     if tuple(mask.shape) not in ((batch, num, _MASK_CH, ht, wd), (batch * num, _MASK_CH, ht, wd)):
         raise RuntimeError("mask must be (%d,%d,%d,%d,%d), got %s" % (batch, num, _MASK_CH, ht, wd, tuple(mask.shape)))
     return cvx_upsample(disp.view(batch * num, ht, wd, 1), mask.view(batch * num, _MASK_CH, ht, wd)).view(
@@ -166,19 +142,17 @@ def upsample_disps_(disps_up, disps, ix, mask):
         raise RuntimeError("disps_up must be (N,8ht,8wd) = %s, got %s" % ((N, 8 * ht, 8 * wd), tuple(disps_up.shape)))
     if ix.dim() != 1:
         raise RuntimeError("ix must be 1-D, got %s" % (tuple(ix.shape),))
-    _contiguous(disps_up, "disps_up", disps, "disps", ix, "ix", mask, "mask")
-    _check_float(disps_up, "disps_up")
-    _check_float(disps, "disps")
-    _index(ix, "ix")
+    named = [(disps_up, "disps_up"), (disps, "disps"), (ix, "ix"), (mask, "mask")]
+    check_contiguous(named)
+    check_dtype(named[:2], torch.float32)
+    check_dtype(named[2:3], torch.int64)
     U = ix.shape[0]
     _check_mask(mask, U, ht, wd)
     flags = _mask_flags(mask)
-    _check_no_grad("upsample_disps_", disps_up, disps, mask)
-    _check_device([(disps_up, "disps_up"), (disps, "disps"), (ix, "ix"), (mask, "mask")])
+    check_no_grad("upsample_disps_", named)
+    check_device(named)
     if U * N * ht * wd == 0:
         return disps_up
-    with torch.cuda.device(disps.device):
-        rc = _lib.load().lgu_upsample_disps_f32(_ptr(disps), N, ht, wd, _ptr(ix), U, _ptr(mask), flags, _ptr(disps_up),
-                                                _stream(disps))
-    _lib.check(rc, "upsample_disps_")
+    launch("lgu_upsample_disps_f32", "upsample_disps_", disps.device, _ptr(disps), N, ht, wd, _ptr(ix), U, _ptr(mask), flags,
+           _ptr(disps_up), _stream(disps))
     return disps_up

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _check, _check_dtype, _ptr, _stream
+from ._host import CurrentDevice, check_operands
+from ._host import ptr as _ptr, stream as _stream
 
 _ALPHA = 0.05  # droid_kernels.cu:1394
 
@@ -255,16 +256,16 @@ def _run(pl, lib, poses, disps, intrinsics, disps_sens, targets, weights, eta_v,
 def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, motion_only, _hooks=None):
     """`_hooks` (sharded.sharded_ba_split only): (reduce_system(Ad, b), after_depth(disps)) called once per iteration, and
     `eta` may then be a callable kx -> (K, ht, wd) giving the damping rows of this call's depth frames."""
-    named = [poses, "poses", disps, "disps", intrinsics, "intrinsics", disps_sens, "disps_sens"]
+    named = [(poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (disps_sens, "disps_sens")]
     if ii.numel():   # (a rank of a split BA may own no edge)
-        named += [targets, "targets", weights, "weights"]
-    _check(*named)
-    _check_dtype(ii, "ii", torch.int64)
-    _check_dtype(jj, "jj", torch.int64)
+        named += [(targets, "targets"), (weights, "weights")]
+    check_operands(named)
+    check_operands([(ii, "ii")], torch.int64)
+    check_operands([(jj, "jj")], torch.int64)
     lib = _lib.load()
     dev = poses.device
     HW = disps.shape[1] * disps.shape[2]
-    with torch.cuda.device(dev):
+    with CurrentDevice(dev):
         # graph bookkeeping on the host (numpy): built once per edge set, reused while the graph does not change
         pl = _plan_for(lib, ii, jj, t0, t1, motion_only, dev)
         eta_v = None

@@ -23,11 +23,10 @@ import ctypes
 import torch
 
 from . import _lib
-from .aggregate import _contiguous, _dtype_name
-from .geom import _check_device, _check_no_grad
-from .ops import _CurrentDevice, _ptr, _stream
+from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, dtype_name,
+                    fused_dtype, is_conv, launch, typed, unbind)
+from ._host import ptr as _ptr, stream as _stream
 
-_SUFFIX = {torch.float32: "f32", torch.float16: "h16"}
 IMAGENET_MEAN = (0.485, 0.456, 0.406)     # motion_filter.py:30-31, RGB
 IMAGENET_STD = (0.229, 0.224, 0.225)
 LAYERS = ("layer1", "layer2", "layer3")
@@ -52,8 +51,7 @@ def instance_norm_relu(a, residual=None, *, norm_residual=False, relu=True, eps=
     half result is rounded once."""
     if a.dim() != 4:
         raise RuntimeError("a must be (N,C,H,W), got %s" % (tuple(a.shape),))
-    if a.dtype not in _SUFFIX:
-        raise RuntimeError("expected scalar type Float or Half but found %s (a)" % _dtype_name(a.dtype))
+    check_dtype([(a, "a")], FLOAT_OR_HALF)
     if residual is None:
         if norm_residual:
             raise ValueError("norm_residual=True needs a residual")
@@ -63,37 +61,32 @@ def instance_norm_relu(a, residual=None, *, norm_residual=False, relu=True, eps=
             raise ValueError("relu=False is served without a residual only")
         mode = 2 if norm_residual else 1
     named = [(a, "a")] + ([(residual, "residual")] if residual is not None else []) + ([(out, "out")] if out is not None else [])
-    for t, name in named[1:]:
-        if tuple(t.shape) != tuple(a.shape):
-            raise RuntimeError("%s must be %s, got %s" % (name, tuple(a.shape), tuple(t.shape)))
-        if t.dtype != a.dtype:
-            raise RuntimeError("expected scalar type %s but found %s (%s)" % (_dtype_name(a.dtype), _dtype_name(t.dtype), name))
+    for pair in named[1:]:
+        check_shape([pair], a.shape)
+        check_dtype([pair], a.dtype)
     N, C, H, W = a.shape
     hw = H * W
     if hw == 1:
         raise ValueError("Expected more than 1 spatial element when training, got input size %s" % (a.size(),))
     if not eps >= 0:
         raise ValueError("eps must be >= 0, got %r" % (eps,))
-    _contiguous(*[x for p in named for x in p])
-    _check_no_grad("instance_norm_relu", *[t for t, _ in named])
-    _check_device(named)
+    check_contiguous(named)
+    check_no_grad("instance_norm_relu", named)
+    check_device(named)
     if out is None:
         out = torch.empty_like(a)
     if N * C == 0:
         return out
     if hw == 0:
         raise RuntimeError("instance_norm_relu: empty planes (H*W = 0), the statistics are undefined")
-    return _launch(a, residual, out, mode, float(eps))
+    return _instnorm(a, residual, out, mode, float(eps))
 
 
-def _launch(a, b, out, mode, eps):
+def _instnorm(a, b, out, mode, eps):
     """The call itself, for arguments already checked (instance_norm_relu, FeatureEncoder._fused)."""
-    with _CurrentDevice(a.device):
-        rc = getattr(_lib.load(), "lgu_instnorm_relu_" + _SUFFIX[a.dtype])(
-            a.data_ptr(), b.data_ptr() if b is not None else None, out.data_ptr(), a.shape[0] * a.shape[1],
-            a.shape[2] * a.shape[3], eps, mode, torch.cuda.current_stream(a.device).cuda_stream)
-    if rc:
-        _lib.check(rc, "instance_norm_relu")
+    launch(typed("lgu_instnorm_relu", a.dtype), "instance_norm_relu", a.device, a.data_ptr(),
+           b.data_ptr() if b is not None else None, out.data_ptr(), a.shape[0] * a.shape[1], a.shape[2] * a.shape[3], eps, mode,
+           torch.cuda.current_stream(a.device).cuda_stream)
     return out
 
 
@@ -106,21 +99,19 @@ def normalize_images(image, mean=IMAGENET_MEAN, std=IMAGENET_STD):
     if image.dim() != 4 or image.shape[1] != 3:
         raise RuntimeError("image must be (N,3,H,W), got %s" % (tuple(image.shape),))
     if image.dtype != torch.uint8:
-        raise RuntimeError("expected scalar type Byte but found %s (image)" % _dtype_name(image.dtype))
+        raise RuntimeError("expected scalar type Byte but found %s (image)" % dtype_name(image.dtype))
     if len(mean) != 3 or len(std) != 3:
         raise RuntimeError("mean and std must have 3 entries")
     if not image.is_cuda:
         image = image.contiguous().to(torch.device("cuda"))
-    _contiguous(image, "image")
+    check_contiguous([(image, "image")])
     N, _, H, W = image.shape
     out = torch.empty((1, N, 3, H, W), dtype=torch.float32, device=image.device)
     if N * H * W == 0:
         return out
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    with _CurrentDevice(image.device):
-        rc = _lib.load().lgu_image_normalize_u8(_ptr(image), _ptr(out), N, H * W, m, s, _stream(image))
-    _lib.check(rc, "normalize_images")
+    launch("lgu_image_normalize_u8", "normalize_images", image.device, _ptr(image), _ptr(out), N, H * W, m, s, _stream(image))
     return out
 
 
@@ -133,9 +124,7 @@ def _check_norm(m, channels, name):
 
 
 def _check_conv(m, cin, cout, k, stride, pad, name):
-    if (not isinstance(m, torch.nn.Conv2d) or m.in_channels != cin or m.out_channels != cout or m.kernel_size != (k, k)
-            or m.stride != (stride, stride) or m.padding != (pad, pad) or m.dilation != (1, 1) or m.groups != 1
-            or m.padding_mode != "zeros"):
+    if not is_conv(m, cin, cout, k, stride, pad):
         raise RuntimeError("FeatureEncoder: %s must be Conv2d(%d, %d, %d, stride=%d, padding=%d)"
                            % (name, cin, cout, k, stride, pad))
 
@@ -216,13 +205,10 @@ class FeatureEncoder:
         params = [p for c in self._convs() for p in (c.weight, c.bias) if p is not None]
         if any(p.dtype != torch.float32 or p.device != x.device or not p.is_contiguous() for p in params):
             return None
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            return None
-        if torch.is_autocast_enabled("cuda"):
-            if torch.get_autocast_dtype("cuda") != torch.float16 or x.dtype not in (torch.float16, torch.float32):
-                return None
-            return torch.float16
-        return torch.float32 if x.dtype == torch.float32 else None
+        dt = fused_dtype([x] + params)
+        if dt == torch.float16:                  # autocast casts float32 images on the way into conv1
+            return dt if x.dtype in FLOAT_OR_HALF else None
+        return dt if x.dtype == dt else None
 
     def _fused(self, x, dt):
         """The fused forward, or None if a convolution returned something the kernels do not take (then nothing of the
@@ -236,21 +222,21 @@ class FeatureEncoder:
         y = m.conv1(x.view(b * n, c1, h1, w1))
         if not ok(y):
             return None
-        y = _launch(y, None, y, 0, m.norm1.eps)
+        y = _instnorm(y, None, y, 0, m.norm1.eps)
         for blk in self.blocks:
             t = blk.conv1(y)
             if not ok(t):
                 return None
-            t = blk.conv2(_launch(t, None, t, 0, blk.norm1.eps))
+            t = blk.conv2(_instnorm(t, None, t, 0, blk.norm1.eps))
             if not ok(t):
                 return None
             if blk.downsample is None:
-                y = _launch(t, y, t, 1, blk.norm2.eps)
+                y = _instnorm(t, y, t, 1, blk.norm2.eps)
             else:
                 r = blk.downsample[0](y)
                 if not ok(r):
                     return None
-                y = _launch(t, r, t, 2, blk.norm2.eps)
+                y = _instnorm(t, r, t, 2, blk.norm2.eps)
         y = m.conv2(y)
         return y.view(b, n, y.shape[1], y.shape[2], y.shape[3])
 
@@ -270,15 +256,9 @@ def install(module):
     """Bind a FeatureEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
     unchanged), so every caller of the encoder reaches the fused path.  Returns the wrapper; a second call returns the
     one already installed."""
-    cur = module.__dict__.get("forward")
-    if isinstance(cur, FeatureEncoder):
-        return cur
-    wrapper = FeatureEncoder(module)
-    module.forward = wrapper
-    return wrapper
+    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module))
 
 
 def uninstall(module):
     """Undo `install`: the class's forward is used again."""
-    if isinstance(module.__dict__.get("forward"), FeatureEncoder):
-        del module.forward
+    unbind(module, "forward", FeatureEncoder)

@@ -15,9 +15,9 @@ mode is on.  There is no fp32 kernel: fp32 evaluation is the module's own forwar
 import torch
 
 from . import _lib
-from .aggregate import _contiguous, _dtype_name
-from .geom import _check_device, _check_no_grad
-from .ops import _ptr, _stream
+from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
+                    is_conv, launch, param_key, unbind)
+from ._host import stream as _stream
 
 CIN, COUT, KW, PAD, C2 = 4, 128, 7, 3, 64
 WPACK_HALVES = 28672             # include/lgu_corr.h LGU_FLOW_CONV7_WPACK_HALVES = 7 * 8 * 64 * 8
@@ -32,10 +32,8 @@ def pack_conv7(weight, bias):
     """(wpack (7,8,64,8) half, bias_h (128) half) of a Conv2d(4, 128, 7) weight (128,4,7,7) and bias (128), on the weight's
     device.  wpack[ky, ct, l, j] = half(weight)[16 ct + (l & 15), k % 4, ky, k // 4] with k = 8 (l >> 4) + j, and 0 where
     k // 4 == 7: the B operand of v_mfma_f32_16x16x32_f16, one window row per K step."""
-    if tuple(weight.shape) != (COUT, CIN, KW, KW):
-        raise RuntimeError("weight must be %s, got %s" % ((COUT, CIN, KW, KW), tuple(weight.shape)))
-    if tuple(bias.shape) != (COUT,):
-        raise RuntimeError("bias must be %s, got %s" % ((COUT,), tuple(bias.shape)))
+    check_shape([(weight, "weight")], (COUT, CIN, KW, KW))
+    check_shape([(bias, "bias")], (COUT,))
     with torch.no_grad():
         wh = weight.detach().to(torch.float16)
         slots = torch.zeros((COUT, KW, KW + 1, CIN), dtype=torch.float16, device=wh.device)   # [co][ky][x-slot][c]
@@ -55,16 +53,13 @@ def flow_conv7_relu(x, wpack, bias_h):
         raise RuntimeError("x must be (N,%d,H,W), got %s" % (CIN, tuple(x.shape)))
     if wpack.numel() != WPACK_HALVES:
         raise RuntimeError("wpack must hold %d halves (pack_conv7), got %s" % (WPACK_HALVES, tuple(wpack.shape)))
-    if tuple(bias_h.shape) != (COUT,):
-        raise RuntimeError("bias_h must be %s, got %s" % ((COUT,), tuple(bias_h.shape)))
-    _contiguous(x, "x", wpack, "wpack", bias_h, "bias_h")
-    if x.dtype not in (torch.float32, torch.float16):
-        raise RuntimeError("expected scalar type Float or Half but found %s (x)" % _dtype_name(x.dtype))
-    for t, name in ((wpack, "wpack"), (bias_h, "bias_h")):
-        if t.dtype != torch.float16:
-            raise RuntimeError("expected scalar type Half but found %s (%s)" % (_dtype_name(t.dtype), name))
-    _check_no_grad("flow_conv7_relu", x, wpack, bias_h)
-    _check_device([(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")])
+    named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
+    check_shape(named[2:], (COUT,))
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:], torch.float16)
+    check_no_grad("flow_conv7_relu", named)
+    check_device(named)
     N, _, H, W = x.shape
     out = torch.empty((N, COUT, H, W), dtype=torch.float16, device=x.device)
     if N == 0:
@@ -74,15 +69,8 @@ def flow_conv7_relu(x, wpack, bias_h):
     if x.dtype == torch.float16:
         x = x.float()
     args = _lib.FlowConv7Args(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), N, H, W)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().lgu_flow_conv7_relu_h16(args, _stream(x)), "flow_conv7_relu")
+    launch("lgu_flow_conv7_relu_h16", "flow_conv7_relu", x.device, args, _stream(x))
     return out
-
-
-def _is_conv(m, cin, cout, k, pad):
-    return (isinstance(m, torch.nn.Conv2d) and m.in_channels == cin and m.out_channels == cout and m.kernel_size == (k, k)
-            and m.padding == (pad, pad) and m.stride == (1, 1) and m.dilation == (1, 1) and m.groups == 1
-            and m.bias is not None and m.padding_mode == "zeros")
 
 
 class FlowEncoder:
@@ -99,8 +87,8 @@ class FlowEncoder:
 
     def __init__(self, module):
         ok = isinstance(module, torch.nn.Sequential) and len(module) == 4
-        ok = ok and _is_conv(module[0], CIN, COUT, KW, PAD) and isinstance(module[1], torch.nn.ReLU)
-        ok = ok and _is_conv(module[2], COUT, C2, 3, 1) and isinstance(module[3], torch.nn.ReLU)
+        ok = ok and is_conv(module[0], CIN, COUT, KW, pad=PAD, bias=True) and isinstance(module[1], torch.nn.ReLU)
+        ok = ok and is_conv(module[2], COUT, C2, 3, pad=1, bias=True) and isinstance(module[3], torch.nn.ReLU)
         if not ok:
             raise RuntimeError("FlowEncoder: the module must be Sequential(Conv2d(4, 128, 7, padding=3), ReLU, "
                                "Conv2d(128, 64, 3, padding=1), ReLU) with biases")
@@ -112,7 +100,7 @@ class FlowEncoder:
     def packed(self):
         """(wpack, bias_h) of the first layer, cached."""
         c1 = self.module[0]
-        key = tuple((t.data_ptr(), t._version, t.device) for t in (c1.weight, c1.bias))
+        key = param_key((c1.weight, c1.bias))
         if key != self._key:
             self._packed, self._key = pack_conv7(c1.weight, c1.bias), key
         return self._packed
@@ -125,9 +113,7 @@ class FlowEncoder:
         params = [self.module[0].weight, self.module[0].bias, self.module[2].weight, self.module[2].bias]
         if any(p.dtype != torch.float32 or p.device != x.device for p in params):
             return False
-        if torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params):
-            return False
-        if not torch.is_autocast_enabled("cuda") or torch.get_autocast_dtype("cuda") != torch.float16:
+        if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
             return False
         return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS
 
@@ -144,15 +130,9 @@ class FlowEncoder:
 def install(module):
     """Bind a FlowEncoder as `module.forward` (an instance attribute: parameters and state_dict keys are unchanged), so
     the reference's UpdateModule.forward reaches the fused path.  Returns the wrapper."""
-    cur = module.__dict__.get("forward")
-    if isinstance(cur, FlowEncoder):
-        return cur
-    wrapper = FlowEncoder(module)
-    module.forward = wrapper
-    return wrapper
+    return bind(module, "forward", FlowEncoder, lambda _: FlowEncoder(module))
 
 
 def uninstall(module):
     """Undo `install`: the class's forward is used again."""
-    if isinstance(module.__dict__.get("forward"), FlowEncoder):
-        del module.forward
+    unbind(module, "forward", FlowEncoder)

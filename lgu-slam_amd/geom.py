@@ -18,40 +18,28 @@ Kernels are enqueued on the current stream of the inputs' device, without host s
 """
 import torch
 
-from . import _lib
-from .ops import _TORCH_NAME, _ptr, _stream
+from ._host import check_contiguous, check_device, check_dtype, check_no_grad, launch
+from ._host import ptr as _ptr, stream as _stream
 
 
-def _check_inputs(*named):
-    """_check_inputs(poses, "poses", ..., ii, "ii"): CHECK_INPUT (src/droid.cpp:84-85, "x must be contiguous") on every
-    argument in the reference's order, then the dtypes of the reference's accessors: float32 data, int64 (`long`)
-    indices — an argument named ii, jj or ix is an index.  Returns the pairs for _check_device, which runs after the
-    shape checks: every argument error is raised before anything is launched, and without a device."""
-    pairs = list(zip(named[0::2], named[1::2]))
-    for t, name in pairs:
-        if not t.is_contiguous():
-            raise RuntimeError("%s must be contiguous" % name)
-    for t, name in pairs:
-        want = torch.int64 if name in _INDEX_NAMES else torch.float32
-        if t.dtype != want:
-            raise RuntimeError("expected scalar type %s but found %s (%s)" % (_TORCH_NAME[want], _TORCH_NAME.get(t.dtype, str(t.dtype)),
-                                                                         name))
-    return pairs
+def _operands(data, index=(), tail=()):
+    """CHECK_INPUT (src/droid.cpp:84-85, "x must be contiguous") on every argument in the reference's order, then the dtypes
+    of the reference's accessors: float32 for `data` and `tail`, int64 (`long`) for `index`.  Returns the pairs for
+    check_device, which runs after the shape checks: every argument error is raised before anything is launched, and
+    without a device."""
+    named = list(data) + list(index) + list(tail)
+    check_contiguous(named)
+    check_dtype(data, torch.float32)
+    check_dtype(index, torch.int64)
+    check_dtype(tail, torch.float32)
+    return named
 
 
-def _check_device(pairs):
-    for t, name in pairs:
-        if not t.is_cuda:
-            raise RuntimeError("%s must be a HIP device tensor: lgu_slam_amd has no CPU fallback" % name)
-    for t, name in pairs:
-        if t.device != pairs[0][0].device:
-            raise RuntimeError("%s is on %s, expected %s" % (name, t.device, pairs[0][0].device))
+def _video(poses, disps, intrinsics):
+    return [(poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")]
 
 
-_INDEX_NAMES = ("ii", "jj", "ix")
-
-
-def _check_geometry(poses, disps, intrinsics):
+def check_geometry(poses, disps, intrinsics):
     if poses.dim() != 2 or poses.shape[1] != 7:
         raise RuntimeError("poses must be (N,7) = t, q(xyzw), got %s" % (tuple(poses.shape),))
     if disps.dim() != 3:
@@ -69,37 +57,33 @@ def _pairs(ii, jj):
 def frame_distance(poses, disps, intrinsics, ii, jj, beta):
     """dist[k] (num,): mean flow magnitude from frame ii[k] to jj[k], a beta : 1-beta blend of the full transform and
     the translation alone, or 1000 when less than 75 % of the weight has depth > MIN_DEPTH (:518-658)."""
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj")
-    _check_geometry(poses, disps, intrinsics)
+    named = _operands(_video(poses, disps, intrinsics), [(ii, "ii"), (jj, "jj")])
+    check_geometry(poses, disps, intrinsics)
     num = _pairs(ii, jj)
-    _check_device(named)
+    check_device(named)
     dist = torch.empty((num,), dtype=torch.float32, device=poses.device)
     if num == 0:
         return dist
     Nd, ht, wd = disps.shape
-    with torch.cuda.device(poses.device):
-        rc = _lib.load().lgu_frame_distance_f32(_ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd, _ptr(intrinsics),
-                                                _ptr(ii), _ptr(jj), num, float(beta), _ptr(dist), _stream(poses))
-    _lib.check(rc, "frame_distance")
+    launch("lgu_frame_distance_f32", "frame_distance", poses.device, _ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd,
+           _ptr(intrinsics), _ptr(ii), _ptr(jj), num, float(beta), _ptr(dist), _stream(poses))
     return dist
 
 
 def projmap(poses, disps, intrinsics, ii, jj):
     """[coords (num,ht,wd,3), valid (num,ht,wd,1)]: pixels of frame ii[k] projected into jj[k] (:427-516).  coords =
     (u, v) unless the point's depth exceeds 0.01, then its projection; channel 2 is 0.  valid = depth > MIN_DEPTH."""
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj")
-    _check_geometry(poses, disps, intrinsics)
+    named = _operands(_video(poses, disps, intrinsics), [(ii, "ii"), (jj, "jj")])
+    check_geometry(poses, disps, intrinsics)
     num = _pairs(ii, jj)
-    _check_device(named)
+    check_device(named)
     Nd, ht, wd = disps.shape
     coords = torch.empty((num, ht, wd, 3), dtype=torch.float32, device=poses.device)
     valid = torch.empty((num, ht, wd, 1), dtype=torch.float32, device=poses.device)
     if num == 0 or ht * wd == 0:
         return [coords, valid]
-    with torch.cuda.device(poses.device):
-        rc = _lib.load().lgu_projmap_f32(_ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd, _ptr(intrinsics),
-                                         _ptr(ii), _ptr(jj), num, _ptr(coords), _ptr(valid), _stream(poses))
-    _lib.check(rc, "projmap")
+    launch("lgu_projmap_f32", "projmap", poses.device, _ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd,
+           _ptr(intrinsics), _ptr(ii), _ptr(jj), num, _ptr(coords), _ptr(valid), _stream(poses))
     return [coords, valid]
 
 
@@ -107,22 +91,20 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
     """counter (num,ht,wd): for every pixel of frame ix[b], how many of the neighbours ix-1, ix-2, ix-3, ix+3, ix+4,
     ix+5 inside the buffer see a disparity of one of the four pixels around its projection within thresh[b] (compared
     as |1/d_proj - 1/d_corner| in double) (:661-776)."""
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ix, "ix", thresh, "thresh")
-    _check_geometry(poses, disps, intrinsics)
+    named = _operands(_video(poses, disps, intrinsics), [(ix, "ix")], [(thresh, "thresh")])
+    check_geometry(poses, disps, intrinsics)
     if ix.dim() != 1:
         raise RuntimeError("ix must be 1-D, got %s" % (tuple(ix.shape),))
     num = ix.shape[0]
     if thresh.dim() != 1 or thresh.shape[0] < num:
         raise RuntimeError("thresh must be 1-D with one entry per index of ix (%d), got %s" % (num, tuple(thresh.shape)))
-    _check_device(named)
+    check_device(named)
     Nd, ht, wd = disps.shape
     counter = torch.empty((num, ht, wd), dtype=torch.float32, device=disps.device)
     if num == 0 or ht * wd == 0:
         return counter
-    with torch.cuda.device(disps.device):
-        rc = _lib.load().lgu_depth_filter_f32(_ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd, _ptr(intrinsics),
-                                              _ptr(ix), _ptr(thresh), num, _ptr(counter), _stream(disps))
-    _lib.check(rc, "depth_filter")
+    launch("lgu_depth_filter_f32", "depth_filter", disps.device, _ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd,
+           _ptr(intrinsics), _ptr(ix), _ptr(thresh), num, _ptr(counter), _stream(disps))
     return counter
 
 
@@ -130,17 +112,15 @@ def iproj(poses, disps, intrinsics):
     """points (Nd,ht,wd,3): every pixel back-projected with its disparity and moved by poses[n],
     act_se3(T_n, (x, y, 1, d))[0:3] / d (:779-851).  The reference's callers pass camera-to-world poses:
     iproj(se3_inverse(poses), disps, intrinsics)."""
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics")
-    _check_geometry(poses, disps, intrinsics)
-    _check_device(named)
+    named = _operands(_video(poses, disps, intrinsics))
+    check_geometry(poses, disps, intrinsics)
+    check_device(named)
     Nd, ht, wd = disps.shape
     points = torch.empty((Nd, ht, wd, 3), dtype=torch.float32, device=disps.device)
     if Nd == 0 or ht * wd == 0:
         return points
-    with torch.cuda.device(disps.device):
-        rc = _lib.load().lgu_iproj_f32(_ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd, _ptr(intrinsics), _ptr(points),
-                                       _stream(disps))
-    _lib.check(rc, "iproj")
+    launch("lgu_iproj_f32", "iproj", disps.device, _ptr(poses), poses.shape[0], _ptr(disps), Nd, ht, wd, _ptr(intrinsics),
+           _ptr(points), _stream(disps))
     return points
 
 
@@ -165,12 +145,6 @@ REPROJ_JACOBIAN, REPROJ_DEPTH = 1, 2     # include/lgu_corr.h LGU_REPROJ_*
 def _pose_tensor(poses):
     """A (B,N,7) tensor as it is, or the `.data` of a group object (a lietorch SE3)."""
     return poses if isinstance(poses, torch.Tensor) else poses.data
-
-
-def _check_no_grad(what, *tensors):
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("%s has no autograd: its outputs would carry no gradient. Call it under torch.no_grad() or "
-                           "pass detached inputs" % what)
 
 
 def _check_batched(poses, disps, intrinsics, ii, jj):
@@ -202,10 +176,10 @@ def projective_transform(poses, disps, intrinsics, ii, jj, jacobian=False, retur
     stereo baseline t = (-0.1, 0, 0).  An index outside [0, min of the three frame counts) gives NaN values and valid 0.
     Quaternions are used as given (lietorch may normalise non-unit ones)."""
     poses = _pose_tensor(poses)
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj")
+    named = _operands(_video(poses, disps, intrinsics), [(ii, "ii"), (jj, "jj")])
     num = _check_batched(poses, disps, intrinsics, ii, jj)
-    _check_no_grad("projective_transform", poses, disps, intrinsics)
-    _check_device(named)
+    check_no_grad("projective_transform", named)
+    check_device(named)
     B, Np, Nd, Ni, ht, wd, num = _sizes(poses, disps, intrinsics, num)
     dev = disps.device
     C = 3 if return_depth else 2
@@ -218,11 +192,8 @@ def projective_transform(poses, disps, intrinsics, ii, jj, jacobian=False, retur
     if B * num * ht * wd > 0:
         flags = (REPROJ_JACOBIAN if jacobian else 0) | (REPROJ_DEPTH if return_depth else 0)
         jac_ptrs = (_ptr(Ji), _ptr(Jj), _ptr(Jz)) if jacobian else (None, None, None)
-        with torch.cuda.device(dev):
-            rc = _lib.load().lgu_projective_transform_f32(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
-                                                          B, Np, Nd, Ni, ht, wd, num, flags, _ptr(coords), _ptr(valid),
-                                                          *jac_ptrs, _stream(disps))
-        _lib.check(rc, "projective_transform")
+        launch("lgu_projective_transform_f32", "projective_transform", dev, _ptr(poses), _ptr(disps), _ptr(intrinsics),
+               _ptr(ii), _ptr(jj), B, Np, Nd, Ni, ht, wd, num, flags, _ptr(coords), _ptr(valid), *jac_ptrs, _stream(disps))
     if jacobian:
         return coords, valid, (Ji, Jj, Jz)
     return coords, valid
@@ -241,22 +212,20 @@ def motion_features(poses, disps, intrinsics, ii, jj, target, clamp=64.0):
     cat([coords1 - coords0, target - coords1], -1).permute(0,1,4,2,3).clamp(-clamp, clamp) (a NaN stays NaN).
     Arguments as projective_transform's; target (B,E,ht,wd,2) float32."""
     poses = _pose_tensor(poses)
-    named = _check_inputs(poses, "poses", disps, "disps", intrinsics, "intrinsics", ii, "ii", jj, "jj", target, "target")
+    named = _operands(_video(poses, disps, intrinsics), [(ii, "ii"), (jj, "jj")], [(target, "target")])
     num = _check_batched(poses, disps, intrinsics, ii, jj)
     B, Np, Nd, Ni, ht, wd, num = _sizes(poses, disps, intrinsics, num)
     if tuple(target.shape) != (B, num, ht, wd, 2):
         raise RuntimeError("target must be (B,E,ht,wd,2) = %s, got %s" % ((B, num, ht, wd, 2), tuple(target.shape)))
     if not float(clamp) >= 0:
         raise RuntimeError("clamp must be a non-negative bound, got %r" % (clamp,))
-    _check_no_grad("motion_features", poses, disps, intrinsics, target)
-    _check_device(named)
+    check_no_grad("motion_features", named)
+    check_device(named)
     dev = disps.device
     coords1 = torch.empty((B, num, ht, wd, 2), dtype=torch.float32, device=dev)
     motn = torch.empty((B, num, 4, ht, wd), dtype=torch.float32, device=dev)
     if B * num * ht * wd > 0:
-        with torch.cuda.device(dev):
-            rc = _lib.load().lgu_motion_features_f32(_ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii), _ptr(jj),
-                                                     _ptr(target), B, Np, Nd, Ni, ht, wd, num, float(clamp), _ptr(coords1),
-                                                     _ptr(motn), None, _stream(disps))
-        _lib.check(rc, "motion_features")
+        launch("lgu_motion_features_f32", "motion_features", dev, _ptr(poses), _ptr(disps), _ptr(intrinsics), _ptr(ii),
+               _ptr(jj), _ptr(target), B, Np, Nd, Ni, ht, wd, num, float(clamp), _ptr(coords1), _ptr(motn), None,
+               _stream(disps))
     return coords1, motn

@@ -17,8 +17,9 @@ device once: the edge count.
 import torch
 
 from . import _lib
-from .geom import _check_device, _check_geometry, frame_distance
-from .ops import _TORCH_NAME, _ptr, _stream
+from ._host import bind, check_contiguous, check_device, check_dtype, launch, unbind
+from ._host import ptr as _ptr, stream as _stream
+from .geom import check_geometry, frame_distance
 
 SMALL_MAX = 4096          # include/lgu_corr.h LGU_PROXIMITY_SMALL_MAX
 MAX_CELLS = 1 << 24
@@ -69,15 +70,6 @@ def capacity(t, t0, t1, rad, stereo, max_factors):
     return min(max(p, max_factors + 2), p + 2 * (t - t0) * (t - t1))
 
 
-def _check_tensor(x, name, dtype, pairs):
-    if not x.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
-    if x.dtype != dtype:
-        raise RuntimeError("expected scalar type %s but found %s (%s)" % (_TORCH_NAME[dtype], _TORCH_NAME.get(x.dtype, str(x.dtype)),
-                                                                         name))
-    pairs.append((x, name))
-
-
 def _pair_list(t, t0, t1, rad, device):
     """(ii, jj, f) of the cells that i - rad < j does not kill (j in [t1, i - rad]), row-major, built on the device from
     sizes the host knows: no synchronisation."""
@@ -112,61 +104,56 @@ def proximity_edges(poses, disps, intrinsics, t, ii_known, jj_known, t0=0, t1=0,
     thresh, beta, stereo = float(thresh), float(beta), bool(stereo)
     if (ii_known is None) != (jj_known is None):
         raise RuntimeError("ii_known and jj_known must both be given or both be None")
-    named = []
-    if dist is None:
-        for x, name in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-            _check_tensor(x, name, torch.float32, named)
-    else:
-        _check_tensor(dist, "dist", torch.float32, named)
+    named = [(poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")] if dist is None else [(dist, "dist")]
+    known = [] if ii_known is None else [(ii_known, "ii_known"), (jj_known, "jj_known")]
+    for pairs, dtype in ((named, torch.float32), (known, torch.int64)):
+        for pair in pairs:                        # contiguity and dtype per tensor, in sequence
+            check_contiguous([pair])
+            check_dtype([pair], dtype)
+    named = named + known
     if ii_known is not None:
-        _check_tensor(ii_known, "ii_known", torch.int64, named)
-        _check_tensor(jj_known, "jj_known", torch.int64, named)
         if ii_known.dim() != 1 or jj_known.dim() != 1 or ii_known.shape[0] != jj_known.shape[0]:
             raise RuntimeError("ii_known and jj_known must be 1-D and of equal length, got %s and %s"
                                % (tuple(ii_known.shape), tuple(jj_known.shape)))
         if ii_known.shape[0] >= 1 << 31:
             raise RuntimeError("proximity_edges: too many known edges")
     if dist is None:
-        _check_geometry(poses, disps, intrinsics)
+        check_geometry(poses, disps, intrinsics)
     elif dist.dim() != 1 or dist.shape[0] != n:
         raise RuntimeError("dist must be 1-D with one value per cell (%d), got %s" % (n, tuple(dist.shape)))
     cap = capacity(t, t0, t1, rad, stereo, max_factors)
     if prefix_len(t, t0, rad, stereo) > 1 << 30:
         raise RuntimeError("proximity_edges: the neighbourhood prefix alone exceeds 2^30 entries")
-    _check_device(named)
+    check_device(named)
     dev = named[0][0].device
     if n == 0:                                    # no rows: the prefix is empty
         return torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        if dist is None:
-            pi, pj, f = _pair_list(t, t0, t1, rad, dev)
-            num = pi.shape[0]
-            dist = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
-            if num:
-                d = frame_distance(poses, disps, intrinsics, torch.cat([pi, pj]), torch.cat([pj, pi]), beta)
-                dist.index_copy_(0, f, .5 * (d[:num] + d[num:]))
-        nk = 0 if ii_known is None else ii_known.shape[0]
-        kii, kjj = (_ptr(ii_known), _ptr(jj_known)) if nk else (None, None)
-        e_ii = torch.empty((cap,), dtype=torch.int64, device=dev)
-        e_jj = torch.empty((cap,), dtype=torch.int64, device=dev)
-        count = torch.empty((1,), dtype=torch.int32, device=dev)
-        lib, st = _lib.load(), _stream(dist)
-        rad = min(rad, t)                         # selects what any larger rad selects; fits the C int
-        if form == "small" or (form is None and n <= SMALL_MAX):
-            rc = lib.lgu_proximity_select_small(_ptr(dist), kii, kjj, nk, t, t0, t1, rad, nms, thresh, max_factors, int(stereo),
-                                                _ptr(e_ii), _ptr(e_jj), cap, _ptr(count), st)
-            _lib.check(rc, "proximity_select_small")
-        else:
-            keys = torch.empty((n,), dtype=torch.int64, device=dev)
-            work = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=dev)
-            rc = lib.lgu_proximity_keys(_ptr(dist), kii, kjj, nk, t, t0, t1, rad, nms, thresh, int(stereo), _ptr(keys),
-                                        _ptr(work), st)
-            _lib.check(rc, "proximity_keys")
-            keys = torch.sort(keys).values.contiguous()
-            rc = lib.lgu_proximity_select_sorted(_ptr(keys), _ptr(work), t, t0, t1, rad, nms, max_factors, int(stereo),
-                                                 _ptr(e_ii), _ptr(e_jj), cap, _ptr(count), st)
-            _lib.check(rc, "proximity_select_sorted")
-        m = int(count.item())                     # the one read of the device
+    if dist is None:
+        pi, pj, f = _pair_list(t, t0, t1, rad, dev)
+        num = pi.shape[0]
+        dist = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
+        if num:
+            d = frame_distance(poses, disps, intrinsics, torch.cat([pi, pj]), torch.cat([pj, pi]), beta)
+            dist.index_copy_(0, f, .5 * (d[:num] + d[num:]))
+    nk = 0 if ii_known is None else ii_known.shape[0]
+    kii, kjj = (_ptr(ii_known), _ptr(jj_known)) if nk else (None, None)
+    e_ii = torch.empty((cap,), dtype=torch.int64, device=dev)
+    e_jj = torch.empty((cap,), dtype=torch.int64, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    st = _stream(dist)
+    rad = min(rad, t)                             # selects what any larger rad selects; fits the C int
+    if form == "small" or (form is None and n <= SMALL_MAX):
+        launch("lgu_proximity_select_small", "proximity_select_small", dev, _ptr(dist), kii, kjj, nk, t, t0, t1, rad, nms, thresh,
+               max_factors, int(stereo), _ptr(e_ii), _ptr(e_jj), cap, _ptr(count), st)
+    else:
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        work = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=dev)
+        launch("lgu_proximity_keys", "proximity_keys", dev, _ptr(dist), kii, kjj, nk, t, t0, t1, rad, nms, thresh, int(stereo),
+               _ptr(keys), _ptr(work), st)
+        keys = torch.sort(keys).values.contiguous()
+        launch("lgu_proximity_select_sorted", "proximity_select_sorted", dev, _ptr(keys), _ptr(work), t, t0, t1, rad, nms,
+               max_factors, int(stereo), _ptr(e_ii), _ptr(e_jj), cap, _ptr(count), st)
+    m = int(count.item())                         # the one read of the device
     return e_ii[:m], e_jj[:m]
 
 
@@ -208,18 +195,11 @@ class ProximityFactors:
 
 def install(graph):
     """Bind a ProximityFactors as `graph.add_proximity_factors` (an instance attribute); returns it."""
-    cur = graph.__dict__.get("add_proximity_factors")
-    if isinstance(cur, ProximityFactors):
-        return cur
-    wrapper = ProximityFactors(graph, previous=cur)
-    graph.add_proximity_factors = wrapper
-    return wrapper
+    return bind(graph, "add_proximity_factors", ProximityFactors, lambda previous: ProximityFactors(graph, previous=previous))
 
 
 def uninstall(graph):
     """Undo `install`: the class's method (or the instance attribute that was there before) is used again."""
-    cur = graph.__dict__.get("add_proximity_factors")
-    if isinstance(cur, ProximityFactors):
-        del graph.add_proximity_factors
-        if cur.previous is not None:
-            graph.add_proximity_factors = cur.previous
+    cur = unbind(graph, "add_proximity_factors", ProximityFactors)
+    if cur is not None and cur.previous is not None:
+        graph.add_proximity_factors = cur.previous

@@ -15,31 +15,14 @@ float16 tensors the half kernels with the reference's autocast rounding points (
 """
 import torch
 
-from . import _lib
-from .aggregate import _contiguous, _dtype_name
-from .geom import _check_device, _check_no_grad
-from .ops import _ptr, _stream
+from ._host import (bind, check_contiguous, check_device, check_dtype, check_no_grad, check_same_dtype, check_shape, fused_dtype,
+                    is_conv, launch, param_key, typed, unbind)
+from ._host import ptr as _ptr, stream as _stream
 
 C, CIN, NKNOT, NBASIS = 128, 448, 10, 6
 K_FEAT = C + C * NBASIS          # 896 features per edge: [silu(x) | B(x)]
 CTX_PIXELS = 256                 # include/lgu_corr.h LGU_KANGRU_CTX_PIXELS
 HEADS = ("kanz_glo", "kanr_glo", "kanq_glo")
-_SUFFIX = {torch.float32: "f32", torch.float16: "h16"}
-
-
-def _dtype(ts, what):
-    dt = ts[0][0].dtype
-    if dt not in _SUFFIX:
-        raise RuntimeError("expected scalar type Float or Half but found %s (%s)" % (_dtype_name(dt), ts[0][1]))
-    for t, name in ts[1:]:
-        if t.dtype != dt:
-            raise RuntimeError("expected scalar type %s but found %s (%s)" % (_dtype_name(dt), _dtype_name(t.dtype), name))
-    return dt
-
-
-def _shape(t, shape, name):
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
 
 
 def _fmap(t, name, channels=C):
@@ -47,9 +30,13 @@ def _fmap(t, name, channels=C):
         raise RuntimeError("%s must be (E,%d,H,W), got %s" % (name, channels, tuple(t.shape)))
 
 
-def _call(fn, dt, what, *args):
-    rc = getattr(_lib.load(), "%s_%s" % (fn, _SUFFIX[dt]))(*args)
-    _lib.check(rc, what)
+def _checked(named, what):
+    """What follows an operator's shape checks when all its operands share one dtype; returns that dtype."""
+    check_contiguous(named)
+    dt = check_same_dtype(named)
+    check_no_grad(what, named)
+    check_device(named)
+    return dt
 
 
 def kangru_context(net, weight, bias):
@@ -57,15 +44,10 @@ def kangru_context(net, weight, bias):
     (128,128,1,1) or (128,128) and bias (128) of net's dtype.  Half: the convolution output with its bias (one rounding,
     as the library adds the bias), the sigmoid, the product and the mean are each rounded to half, as under autocast."""
     _fmap(net, "net")
-    if weight.dim() == 4:
-        _shape(weight, (C, C, 1, 1), "weight")
-    else:
-        _shape(weight, (C, C), "weight")
-    _shape(bias, (C,), "bias")
-    _contiguous(net, "net", weight, "weight", bias, "bias")
-    dt = _dtype([(net, "net"), (weight, "weight"), (bias, "bias")], "kangru_context")
-    _check_no_grad("kangru_context", net, weight, bias)
-    _check_device([(net, "net"), (weight, "weight"), (bias, "bias")])
+    named = [(net, "net"), (weight, "weight"), (bias, "bias")]
+    check_shape(named[1:2], (C, C, 1, 1) if weight.dim() == 4 else (C, C))
+    check_shape(named[2:], (C,))
+    dt = _checked(named, "kangru_context")
     E, _, H, W = net.shape
     glo = torch.empty((E, C), dtype=dt, device=net.device)
     if E == 0:
@@ -73,9 +55,8 @@ def kangru_context(net, weight, bias):
     if H * W == 0:
         raise RuntimeError("kangru_context: empty frame (H*W = 0), the mean is undefined")
     partial = torch.empty((E, (H * W + CTX_PIXELS - 1) // CTX_PIXELS, C), dtype=torch.float32, device=net.device)
-    with torch.cuda.device(net.device):
-        _call("lgu_kangru_context", dt, "kangru_context", _ptr(net), _ptr(weight), _ptr(bias), E, H * W, _ptr(partial),
-              _ptr(glo), _stream(net))
+    launch(typed("lgu_kangru_context", dt), "kangru_context", net.device, _ptr(net), _ptr(weight), _ptr(bias), E, H * W,
+           _ptr(partial), _ptr(glo), _stream(net))
     return glo
 
 
@@ -84,20 +65,19 @@ def kan_heads(glo, grid, wpack):
     knots; wpack (384,896) of glo's dtype from `pack_heads`."""
     if glo.dim() != 2 or glo.shape[1] != C:
         raise RuntimeError("glo must be (E,%d), got %s" % (C, tuple(glo.shape)))
-    _shape(grid, (3, C, NKNOT), "grid")
-    _shape(wpack, (3 * C, K_FEAT), "wpack")
-    _contiguous(glo, "glo", grid, "grid", wpack, "wpack")
-    dt = _dtype([(glo, "glo"), (wpack, "wpack")], "kan_heads")
-    if grid.dtype != torch.float32:
-        raise RuntimeError("expected scalar type Float but found %s (grid)" % _dtype_name(grid.dtype))
-    _check_no_grad("kan_heads", glo, grid, wpack)
-    _check_device([(glo, "glo"), (grid, "grid"), (wpack, "wpack")])
+    named = [(glo, "glo"), (grid, "grid"), (wpack, "wpack")]
+    check_shape(named[1:2], (3, C, NKNOT))
+    check_shape(named[2:], (3 * C, K_FEAT))
+    check_contiguous(named)
+    dt = check_same_dtype([named[0], named[2]])
+    check_dtype(named[1:2], torch.float32)
+    check_no_grad("kan_heads", named)
+    check_device(named)
     E = glo.shape[0]
     out = torch.empty((3, E, C), dtype=dt, device=glo.device)
     if E == 0:
         return out
-    with torch.cuda.device(glo.device):
-        _call("lgu_kan_heads", dt, "kan_heads", _ptr(glo), _ptr(grid), _ptr(wpack), E, _ptr(out), _stream(glo))
+    launch(typed("lgu_kan_heads", dt), "kan_heads", glo.device, _ptr(glo), _ptr(grid), _ptr(wpack), E, _ptr(out), _stream(glo))
     return out
 
 
@@ -106,21 +86,14 @@ def kangru_gates_(net_inp, cz, cr, kz, kr, net):
     (gru_kanBias.py:30-32): net_inp (E,448,H,W); cz, cr, net (E,128,H,W); kz, kr (E,128) broadcast over the pixels."""
     _fmap(net_inp, "net_inp", CIN)
     E, _, H, W = net_inp.shape
-    for t, name in ((cz, "cz"), (cr, "cr"), (net, "net")):
-        _shape(t, (E, C, H, W), name)
-    for t, name in ((kz, "kz"), (kr, "kr")):
-        _shape(t, (E, C), name)
-    named = [(net_inp, "net_inp"), (cz, "cz"), (cr, "cr"), (kz, "kz"), (kr, "kr"), (net, "net")]
-    _contiguous(*[x for p in named for x in p])
-    dt = _dtype(named, "kangru_gates_")
-    _check_no_grad("kangru_gates_", net_inp, cz, cr, kz, kr, net)
-    _check_device(named)
+    check_shape([(cz, "cz"), (cr, "cr"), (net, "net")], (E, C, H, W))
+    check_shape([(kz, "kz"), (kr, "kr")], (E, C))
+    dt = _checked([(net_inp, "net_inp"), (cz, "cz"), (cr, "cr"), (kz, "kz"), (kr, "kr"), (net, "net")], "kangru_gates_")
     z = torch.empty((E, C, H, W), dtype=dt, device=net.device)
     if E * H * W == 0:
         return z
-    with torch.cuda.device(net.device):
-        _call("lgu_kangru_gates", dt, "kangru_gates_", _ptr(cz), _ptr(cr), _ptr(kz), _ptr(kr), _ptr(net), E, H * W, _ptr(z),
-              _ptr(net_inp), _stream(net))
+    launch(typed("lgu_kangru_gates", dt), "kangru_gates_", net.device, _ptr(cz), _ptr(cr), _ptr(kz), _ptr(kr), _ptr(net), E,
+           H * W, _ptr(z), _ptr(net_inp), _stream(net))
     return z
 
 
@@ -129,20 +102,14 @@ def kangru_blend(cq, kq, z, net):
     kq (E,128)."""
     _fmap(cq, "cq")
     E, _, H, W = cq.shape
-    for t, name in ((z, "z"), (net, "net")):
-        _shape(t, (E, C, H, W), name)
-    _shape(kq, (E, C), "kq")
-    named = [(cq, "cq"), (kq, "kq"), (z, "z"), (net, "net")]
-    _contiguous(*[x for p in named for x in p])
-    dt = _dtype(named, "kangru_blend")
-    _check_no_grad("kangru_blend", cq, kq, z, net)
-    _check_device(named)
+    check_shape([(z, "z"), (net, "net")], (E, C, H, W))
+    check_shape([(kq, "kq")], (E, C))
+    dt = _checked([(cq, "cq"), (kq, "kq"), (z, "z"), (net, "net")], "kangru_blend")
     out = torch.empty((E, C, H, W), dtype=dt, device=net.device)
     if E * H * W == 0:
         return out
-    with torch.cuda.device(net.device):
-        _call("lgu_kangru_blend", dt, "kangru_blend", _ptr(cq), _ptr(kq), _ptr(z), _ptr(net), E, H * W, _ptr(out),
-              _stream(net))
+    launch(typed("lgu_kangru_blend", dt), "kangru_blend", net.device, _ptr(cq), _ptr(kq), _ptr(z), _ptr(net), E, H * W,
+           _ptr(out), _stream(net))
     return out
 
 
@@ -158,9 +125,7 @@ def pack_heads(heads, dtype):
 
 
 def _check_conv(m, cin, cout, k, pad, name):
-    if (not isinstance(m, torch.nn.Conv2d) or m.in_channels != cin or m.out_channels != cout or m.kernel_size != (k, k)
-            or m.padding != (pad, pad) or m.stride != (1, 1) or m.dilation != (1, 1) or m.groups != 1 or m.bias is None
-            or m.padding_mode != "zeros"):
+    if not is_conv(m, cin, cout, k, pad=pad, bias=True):
         raise RuntimeError("KanBiasGRU: %s must be Conv2d(%d, %d, %d, padding=%d) with bias" % (name, cin, cout, k, pad))
 
 
@@ -214,7 +179,7 @@ class KanBiasGRU:
     def packed(self, dtype):
         """(w (128,128), b (128), grid (3,128,10), wpack (384,896)) for the kernels in `dtype`, cached."""
         ts = self._sources()
-        key = (dtype,) + tuple((t.data_ptr(), t._version, t.device) for t in ts)
+        key = (dtype,) + param_key(ts)
         if key != self._key:
             m = self.module
             with torch.no_grad():
@@ -235,12 +200,7 @@ class KanBiasGRU:
             return None
         if any(t.device != net.device or t.dim() != 4 for t in ts):
             return None
-        if torch.is_grad_enabled() and any(t.requires_grad for t in list(ts) + params):
-            return None
-        if torch.is_autocast_enabled("cuda"):
-            dt = torch.float16 if torch.get_autocast_dtype("cuda") == torch.float16 else None
-        else:
-            dt = torch.float32
+        dt = fused_dtype(list(ts) + params)
         if dt is None or any(t.dtype != dt for t in ts):
             return None
         E, ch, H, W = net.shape
@@ -273,15 +233,9 @@ class KanBiasGRU:
 def install(module):
     """Bind a KanBiasGRU as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
     unchanged), so the reference's UpdateModule.forward reaches the fused path.  Returns the wrapper."""
-    cur = module.__dict__.get("forward")
-    if isinstance(cur, KanBiasGRU):
-        return cur
-    wrapper = KanBiasGRU(module)
-    module.forward = wrapper
-    return wrapper
+    return bind(module, "forward", KanBiasGRU, lambda _: KanBiasGRU(module))
 
 
 def uninstall(module):
     """Undo `install`: the class's forward is used again."""
-    if isinstance(module.__dict__.get("forward"), KanBiasGRU):
-        del module.forward
+    unbind(module, "forward", KanBiasGRU)

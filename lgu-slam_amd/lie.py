@@ -30,9 +30,8 @@ import math
 
 import torch
 
-from . import _lib
-from .geom import _check_no_grad
-from .ops import _ptr, _stream
+from ._host import check_no_grad, launch
+from ._host import ptr as _ptr, stream as _stream
 
 LIE_SO3, LIE_SE3 = 0, 1     # include/lgu_corr.h LGU_LIE_*
 
@@ -164,7 +163,7 @@ def _same_kind(what, *tensors):
             raise RuntimeError("%s: operands have different dtypes (%s and %s)" % (what, first.dtype, t.dtype))
         if t.device != first.device:
             raise RuntimeError("%s: operands are on different devices (%s and %s)" % (what, first.device, t.device))
-    _check_no_grad("lie.%s" % what, *tensors)
+    check_no_grad("lie.%s" % what, [(t, "operand") for t in tensors])
 
 
 def _on_hip(t):
@@ -292,10 +291,8 @@ class _Group:
         out = torch.empty(batch + out_last, dtype=torch.float32, device=self.data.device)
         n = int(math.prod(batch))
         if n > 0:
-            with torch.cuda.device(self.data.device):
-                fn = getattr(_lib.load(), "lgu_lie_%s_f32" % name)
-                rc = fn(self._code, *[_ptr(t) for t in flat], n, _ptr(out), _stream(out))
-            _lib.check(rc, "lie.%s" % name)
+            launch("lgu_lie_%s_f32" % name, "lie.%s" % name, self.data.device, self._code, *[_ptr(t) for t in flat], n, _ptr(out),
+                   _stream(out))
         return out
 
     def inv(self):
@@ -321,16 +318,14 @@ class _Group:
     def exp(cls, a):
         if not isinstance(a, torch.Tensor) or not a.is_floating_point() or a.dim() < 1 or a.shape[-1] != cls._T:
             raise ValueError("%s.exp expects a floating-point tensor with last dimension %d" % (cls.__name__, cls._T))
-        _check_no_grad("lie.exp", a)
+        check_no_grad("lie.exp", [(a, "a")])
         if cls._code is None or not _on_hip(a):
             return cls(cls._exp(a))
         ac = a.contiguous()
         out = torch.empty(a.shape[:-1] + (cls._K,), dtype=torch.float32, device=a.device)
         n = int(math.prod(a.shape[:-1]))
         if n > 0:
-            with torch.cuda.device(a.device):
-                rc = _lib.load().lgu_lie_exp_f32(cls._code, _ptr(ac), n, _ptr(out), _stream(out))
-            _lib.check(rc, "lie.exp")
+            launch("lgu_lie_exp_f32", "lie.exp", a.device, cls._code, _ptr(ac), n, _ptr(out), _stream(out))
         return cls(out)
 
     # -- broadcast operations -------------------------------------------------------------------------------------
@@ -356,11 +351,8 @@ class _Group:
         rows = int(math.prod(bshape))
         if rows > 0:
             ng = G.numel() // self._K
-            with torch.cuda.device(x.device):
-                fn = getattr(_lib.load(), entry)
-                rc = fn(self._code, _ptr(G), ng, _ptr(xc), flag if flag is not None else width, rows, g_div, _ptr(out),
-                        _stream(out))
-            _lib.check(rc, "lie.%s" % name)
+            launch(entry, "lie.%s" % name, x.device, self._code, _ptr(G), ng, _ptr(xc), flag if flag is not None else width, rows,
+                   g_div, _ptr(out), _stream(out))
         return out
 
     def act(self, p):

@@ -13,39 +13,11 @@ import ctypes
 import torch
 
 from . import _lib
-
-_vp = ctypes.c_void_p
-
-
-def _check_dtype(t, name, dtype):
-    if not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous" % name)
-    if not t.is_cuda:
-        raise RuntimeError("%s must be a HIP device tensor: lgu_slam_amd has no CPU fallback" % name)
-    if t.dtype != dtype:
-        raise RuntimeError("expected scalar type %s but found %s (%s)" % (str(dtype).replace("torch.", ""), str(t.dtype).replace("torch.", ""), name))
+from ._host import CurrentDevice, check_contiguous, check_operands, dtype_name, launch
+from ._host import _vp, ptr as _ptr, stream as _stream  # noqa: F401  (tests and tools read ops._vp, ops._ptr, ops._stream)
 
 
-def _check(*named):
-    """_check(volume, "volume", coords, "coords", ...): the reference's CHECK_INPUT on every
-    argument first (TORCH_CHECK(x.is_contiguous(), #x " must be contiguous"), droid.cpp:48-49),
-    then what this library additionally requires (HIP device, float32)."""
-    pairs = list(zip(named[0::2], named[1::2]))
-    for t, name in pairs:
-        if not t.is_contiguous():
-            raise RuntimeError("%s must be contiguous" % name)
-    for t, name in pairs:
-        if not t.is_cuda:
-            raise RuntimeError("%s must be a HIP device tensor: lgu_slam_amd has no CPU fallback" % name)
-        if t.dtype != torch.float32:
-            raise RuntimeError("expected scalar type Float but found %s (%s)" % (str(t.dtype).replace("torch.", ""), name))
-
-
-_TORCH_NAME = {torch.float32: "Float", torch.float16: "Half", torch.float64: "Double", torch.bfloat16: "BFloat16",
-               torch.int64: "Long", torch.int32: "Int"}
-
-
-def _via_float(fn, scalar_named, coords, tail, inout=()):
+def _via_float(fn, scalars, coords, tail, inout=()):
     """Half / double operands of the volume-path operators.  The reference dispatches those kernels with
     AT_DISPATCH_FLOATING_TYPES_AND_HALF on the first tensor's type (defCorrSample_kernel.cu:185,219;
     corrSample_kernel.cu:158,189; gaussianAttn.cu:152,187): every scalar_t accessor must then have that dtype
@@ -53,21 +25,18 @@ def _via_float(fn, scalar_named, coords, tail, inout=()):
     these dtypes are served through fp32 copies: computed in fp32 (the arithmetic of the float dispatch), results cast to
     the operands' dtype, in-place side effects (centre zeroing) copied back.  Every reference call site passes float
     (corr.py:30-31,64; gaussianMask_cuda.py:11-12) — this is interface completeness, not a fast path.
-    scalar_named = [t0, "name0", t1, "name1", ...] (t0 decides the dtype); inout = indices into the scalar tensors that
-    the operator modifies."""
-    ts, names = list(scalar_named[0::2]), list(scalar_named[1::2])
+    scalars = [(t0, "name0"), (t1, "name1"), ...] (t0 decides the dtype); inout = indices into the scalar tensors that
+    the operator modifies.  The dtype refusals are torch's accessor errors: they name no argument."""
+    ts = [t for t, _ in scalars]
     dt = ts[0].dtype
-    for t, n in zip(ts, names):
-        if not t.is_contiguous():
-            raise RuntimeError("%s must be contiguous" % n)
+    check_contiguous(scalars)
     if coords is not None:
-        if not coords.is_contiguous():
-            raise RuntimeError("coords must be contiguous")
+        check_contiguous([(coords, "coords")])
         if coords.dtype != torch.float32:
-            raise RuntimeError("expected scalar type Float but found %s" % _TORCH_NAME.get(coords.dtype, str(coords.dtype)))
-    for t, n in zip(ts, names):
+            raise RuntimeError("expected scalar type Float but found %s" % dtype_name(coords.dtype))
+    for t in ts:
         if t.dtype != dt:
-            raise RuntimeError("expected scalar type %s but found %s" % (_TORCH_NAME.get(dt, str(dt)), _TORCH_NAME.get(t.dtype, str(t.dtype))))
+            raise RuntimeError("expected scalar type %s but found %s" % (dtype_name(dt), dtype_name(t.dtype)))
     f32 = [t.float() for t in ts]
     outs = fn(*f32, *([coords] if coords is not None else []), *tail)
     for i in inout:
@@ -78,41 +47,11 @@ def _via_float(fn, scalar_named, coords, tail, inout=()):
 _OTHER_FLOATS = (torch.float16, torch.float64)
 
 
-def _stream(t):
-    return _vp(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-class _CurrentDevice:
-    """Launch guard of the prepared plans: the library launches on the CURRENT device, so a plan whose buffers live on
-    another device switches for the call — and costs one integer comparison when it already is current (the usual
-    one-process-per-GPU case)."""
-
-    def __init__(self, device):
-        self.idx = device.index if device.index is not None else torch.cuda.current_device()
-        self.prev = -1
-
-    def __enter__(self):
-        cur = torch.cuda.current_device()
-        if cur != self.idx:
-            self.prev = cur
-            torch.cuda.set_device(self.idx)
-
-    def __exit__(self, *exc):
-        if self.prev >= 0:
-            torch.cuda.set_device(self.prev)
-            self.prev = -1
-        return False
-
-
-def _ptr(t):
-    return _vp(t.data_ptr())
-
-
 def defCorr_index_forward(volume, coords, offset, radius):
     if volume.dtype in _OTHER_FLOATS:
-        return _via_float(lambda v, o, c, r: defCorr_index_forward(v, c, o, r), [volume, "volume", offset, "offset"], coords,
+        return _via_float(lambda v, o, c, r: defCorr_index_forward(v, c, o, r), [(volume, "volume"), (offset, "offset")], coords,
                           (radius,), inout=(1,))
-    _check(volume, "volume", coords, "coords", offset, "offset")
+    check_operands([(volume, "volume"), (coords, "coords"), (offset, "offset")])
     E, H1, W1, H2, W2 = volume.shape
     rd = 2 * radius + 1
     if tuple(coords.shape) != (E, 2, H1, W1) or offset.numel() != E * H1 * W1 * rd * rd * 2:
@@ -120,35 +59,30 @@ def defCorr_index_forward(volume, coords, offset, radius):
     corr = torch.empty((E, rd, rd, H1, W1), dtype=volume.dtype, device=volume.device)
     if E == 0:
         return [corr]  # no edges: nothing to launch (empty tensors have null data pointers)
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_defcorr_fwd_f32(_ptr(volume), _ptr(coords), _ptr(offset), _ptr(corr),
-                                             E, H1, W1, H2, W2, radius, _stream(volume))
-    _lib.check(rc, "defCorr_index_forward")
+    launch("lgu_defcorr_fwd_f32", "defCorr_index_forward", volume.device, _ptr(volume), _ptr(coords), _ptr(offset),
+           _ptr(corr), E, H1, W1, H2, W2, radius, _stream(volume))
     return [corr]
 
 
 def defCorr_index_backward(volume, coords, offset, corr_grad, radius):
     if volume.dtype in _OTHER_FLOATS:
         return _via_float(lambda v, o, g, c, r: defCorr_index_backward(v, c, o, g, r),
-                          [volume, "volume", offset, "offset", corr_grad, "corr_grad"], coords, (radius,), inout=(1,))
-    _check(volume, "volume", coords, "coords", offset, "offset", corr_grad, "corr_grad")
+                          [(volume, "volume"), (offset, "offset"), (corr_grad, "corr_grad")], coords, (radius,), inout=(1,))
+    check_operands([(volume, "volume"), (coords, "coords"), (offset, "offset"), (corr_grad, "corr_grad")])
     E, H1, W1, H2, W2 = volume.shape
     volume_grad = torch.zeros_like(volume)
     offset_grad = torch.empty_like(offset)
     if E == 0:
         return [volume_grad, offset_grad]
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_defcorr_bwd_f32(_ptr(volume), _ptr(coords), _ptr(offset), _ptr(corr_grad),
-                                             _ptr(volume_grad), _ptr(offset_grad), E, H1, W1, H2, W2, radius,
-                                             _stream(volume))
-    _lib.check(rc, "defCorr_index_backward")
+    launch("lgu_defcorr_bwd_f32", "defCorr_index_backward", volume.device, _ptr(volume), _ptr(coords), _ptr(offset),
+           _ptr(corr_grad), _ptr(volume_grad), _ptr(offset_grad), E, H1, W1, H2, W2, radius, _stream(volume))
     return [volume_grad, offset_grad]
 
 
 def corr_index_forward(volume, coords, radius):
     if volume.dtype in _OTHER_FLOATS:
-        return _via_float(lambda v, c, r: corr_index_forward(v, c, r), [volume, "volume"], coords, (radius,))
-    _check(volume, "volume", coords, "coords")
+        return _via_float(lambda v, c, r: corr_index_forward(v, c, r), [(volume, "volume")], coords, (radius,))
+    check_operands([(volume, "volume"), (coords, "coords")])
     E, H1, W1, H2, W2 = volume.shape
     rd = 2 * radius + 1
     if tuple(coords.shape) != (E, 2, H1, W1):
@@ -156,95 +90,81 @@ def corr_index_forward(volume, coords, radius):
     corr = torch.empty((E, rd, rd, H1, W1), dtype=volume.dtype, device=volume.device)
     if E == 0:
         return [corr]
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_corridx_fwd_f32(_ptr(volume), _ptr(coords), _ptr(corr), E, H1, W1, H2, W2, radius,
-                                             _stream(volume))
-    _lib.check(rc, "corr_index_forward")
+    launch("lgu_corridx_fwd_f32", "corr_index_forward", volume.device, _ptr(volume), _ptr(coords), _ptr(corr), E, H1, W1, H2,
+           W2, radius, _stream(volume))
     return [corr]
 
 
 def corr_index_backward(volume, coords, corr_grad, radius):
     if volume.dtype in _OTHER_FLOATS:
-        return _via_float(lambda v, g, c, r: corr_index_backward(v, c, g, r), [volume, "volume", corr_grad, "corr_grad"], coords,
+        return _via_float(lambda v, g, c, r: corr_index_backward(v, c, g, r), [(volume, "volume"), (corr_grad, "corr_grad")], coords,
                           (radius,))
-    _check(volume, "volume", coords, "coords", corr_grad, "corr_grad")
+    check_operands([(volume, "volume"), (coords, "coords"), (corr_grad, "corr_grad")])
     E, H1, W1, H2, W2 = volume.shape
     volume_grad = torch.zeros_like(volume)
     if E == 0:
         return [volume_grad]
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_corridx_bwd_f32(_ptr(volume), _ptr(coords), _ptr(corr_grad), _ptr(volume_grad),
-                                             E, H1, W1, H2, W2, radius, _stream(volume))
-    _lib.check(rc, "corr_index_backward")
+    launch("lgu_corridx_bwd_f32", "corr_index_backward", volume.device, _ptr(volume), _ptr(coords), _ptr(corr_grad),
+           _ptr(volume_grad), E, H1, W1, H2, W2, radius, _stream(volume))
     return [volume_grad]
 
 
 def gaussianMask(means, covs, volume, radius):
     if volume.dtype in _OTHER_FLOATS:   # gaussianAttn.cu:152 dispatches on volume; means / covs are scalar_t accessors too
-        return _via_float(lambda v, m, c, r: gaussianMask(m, c, v, r), [volume, "volume", means, "means", covs, "covs"], None, (radius,))
-    _check(volume, "volume", means, "means", covs, "covs")
+        return _via_float(lambda v, m, c, r: gaussianMask(m, c, v, r), [(volume, "volume"), (means, "means"), (covs, "covs")], None, (radius,))
+    check_operands([(volume, "volume"), (means, "means"), (covs, "covs")])
     E, H1, W1, H2, W2 = volume.shape
     volume1 = torch.empty_like(volume)
     if E == 0:
         return [volume1]
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_gaussmask_fwd_f32(_ptr(means), _ptr(covs), _ptr(volume), _ptr(volume1),
-                                               E, H1, W1, H2, W2, radius, _stream(volume))
-    _lib.check(rc, "gaussianMask")
+    launch("lgu_gaussmask_fwd_f32", "gaussianMask", volume.device, _ptr(means), _ptr(covs), _ptr(volume), _ptr(volume1), E,
+           H1, W1, H2, W2, radius, _stream(volume))
     return [volume1]
 
 
 def gaussianMask_backward(means, covs, volume, volume_grad, radius):
     if volume.dtype in _OTHER_FLOATS:
         return _via_float(lambda v, m, c, g, r: gaussianMask_backward(m, c, v, g, r),
-                          [volume, "volume", means, "means", covs, "covs", volume_grad, "volume_grad"], None, (radius,))
-    _check(volume, "volume", means, "means", covs, "covs", volume_grad, "volume_grad")
+                          [(volume, "volume"), (means, "means"), (covs, "covs"), (volume_grad, "volume_grad")], None, (radius,))
+    check_operands([(volume, "volume"), (means, "means"), (covs, "covs"), (volume_grad, "volume_grad")])
     E, H1, W1, H2, W2 = volume.shape
     means_grad = torch.empty_like(means)
     covs_grad = torch.empty_like(covs)
     if E == 0:
         return [means_grad, covs_grad]
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_gaussmask_bwd_f32(_ptr(means), _ptr(covs), _ptr(volume), _ptr(volume_grad),
-                                               _ptr(means_grad), _ptr(covs_grad), E, H1, W1, H2, W2, radius,
-                                               _stream(volume))
-    _lib.check(rc, "gaussianMask_backward")
+    launch("lgu_gaussmask_bwd_f32", "gaussianMask_backward", volume.device, _ptr(means), _ptr(covs), _ptr(volume),
+           _ptr(volume_grad), _ptr(means_grad), _ptr(covs_grad), E, H1, W1, H2, W2, radius, _stream(volume))
     return [means_grad, covs_grad]
 
 
 def lowMem_defSample(fmap1, fmap2, coords, offset, radius):
-    _check(fmap1, "fmap1", fmap2, "fmap2", coords, "coords", offset, "offset")
+    check_operands([(fmap1, "fmap1"), (fmap2, "fmap2"), (coords, "coords"), (offset, "offset")])
     B, S, H1, W1, _ = coords.shape
     _, H2, W2, C = fmap2.shape
     rd = 2 * radius + 1
     corr = torch.empty((B, S, rd, rd, H1, W1), dtype=fmap1.dtype, device=fmap1.device)
     if B == 0:
         return [corr]
-    with torch.cuda.device(fmap1.device):
-        rc = _lib.load().lgu_lowmem_defsample_fwd_f32(_ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(offset), _ptr(corr),
-                                                      B, S, H1, W1, H2, W2, C, offset.shape[0], radius,
-                                                      _stream(fmap1))
-    _lib.check(rc, "lowMem_defSample")
+    launch("lgu_lowmem_defsample_fwd_f32", "lowMem_defSample", fmap1.device, _ptr(fmap1), _ptr(fmap2), _ptr(coords),
+           _ptr(offset), _ptr(corr), B, S, H1, W1, H2, W2, C, offset.shape[0], radius, _stream(fmap1))
     return [corr]
 
 
 def altcorr_forward(fmap1, fmap2, coords, radius):
-    _check(fmap1, "fmap1", fmap2, "fmap2", coords, "coords")
+    check_operands([(fmap1, "fmap1"), (fmap2, "fmap2"), (coords, "coords")])
     B, S, H1, W1, _ = coords.shape
     _, H2, W2, C = fmap2.shape
     rd = 2 * radius + 1
     corr = torch.empty((B, S, rd * rd, H1, W1), dtype=fmap1.dtype, device=fmap1.device)
     if B == 0:
         return [corr]
-    with torch.cuda.device(fmap1.device):
-        rc = _lib.load().lgu_altcorr_fwd_f32(_ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr),
-                                             B, S, H1, W1, H2, W2, C, radius, _stream(fmap1))
-    _lib.check(rc, "altcorr_forward")
+    launch("lgu_altcorr_fwd_f32", "altcorr_forward", fmap1.device, _ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr), B, S,
+           H1, W1, H2, W2, C, radius, _stream(fmap1))
     return [corr]
 
 
 def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
-    _check(fmap1, "fmap1", fmap2, "fmap2", coords, "coords", corr_grad, "corr_grad")
+    check_operands([(fmap1, "fmap1"), (fmap2, "fmap2"), (coords, "coords"), (corr_grad, "corr_grad")])
     B, S, H1, W1, _ = coords.shape
     _, H2, W2, C = fmap2.shape
     fmap1_grad = torch.empty_like(fmap1)
@@ -252,11 +172,8 @@ def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
     coords_grad = torch.zeros_like(coords)  # allocated, never written by the reference (altcorr_kernel.cu:336)
     if B == 0:
         return [fmap1_grad, fmap2_grad, coords_grad]
-    with torch.cuda.device(fmap1.device):
-        rc = _lib.load().lgu_altcorr_bwd_f32(_ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr_grad),
-                                             _ptr(fmap1_grad), _ptr(fmap2_grad), B, S, H1, W1, H2, W2, C, radius,
-                                             _stream(fmap1))
-    _lib.check(rc, "altcorr_backward")
+    launch("lgu_altcorr_bwd_f32", "altcorr_backward", fmap1.device, _ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr_grad),
+           _ptr(fmap1_grad), _ptr(fmap2_grad), B, S, H1, W1, H2, W2, C, radius, _stream(fmap1))
     return [fmap1_grad, fmap2_grad, coords_grad]
 
 
@@ -265,36 +182,32 @@ def lowMem_defSample_mixed(fmap1, fmap2, coords, offset, radius):
     `lowMem_defSample(fmap1.float(), fmap2.float(), coords, offset, radius)` — what the reference call site
     does (corr.py:209) — up to fp32 summation order (the contraction runs on the matrix cores with exact half
     products), without materialising the float copies."""
-    _check_dtype(fmap1, "fmap1", torch.float16); _check_dtype(fmap2, "fmap2", torch.float16)
-    _check(coords, "coords", offset, "offset")
+    check_operands([(fmap1, "fmap1")], torch.float16); check_operands([(fmap2, "fmap2")], torch.float16)
+    check_operands([(coords, "coords"), (offset, "offset")])
     B, S, H1, W1, _ = coords.shape
     _, H2, W2, C = fmap2.shape
     rd = 2 * radius + 1
     corr = torch.empty((B, S, rd, rd, H1, W1), dtype=torch.float32, device=fmap1.device)
     if B == 0:
         return [corr]
-    with torch.cuda.device(fmap1.device):
-        rc = _lib.load().lgu_lowmem_defsample_fwd_h16(_ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(offset), _ptr(corr),
-                                                      B, S, H1, W1, H2, W2, C, offset.shape[0], radius, _stream(fmap1))
-    _lib.check(rc, "lowMem_defSample_mixed")
+    launch("lgu_lowmem_defsample_fwd_h16", "lowMem_defSample_mixed", fmap1.device, _ptr(fmap1), _ptr(fmap2), _ptr(coords),
+           _ptr(offset), _ptr(corr), B, S, H1, W1, H2, W2, C, offset.shape[0], radius, _stream(fmap1))
     return [corr]
 
 
 def altcorr_forward_mixed(fmap1, fmap2, coords, radius):
     """altcorr_forward on HALF-precision feature maps, fp32 accumulation/output (= the reference call
     site corr.py:202 on `.float()` copies, up to fp32 summation order)."""
-    _check_dtype(fmap1, "fmap1", torch.float16); _check_dtype(fmap2, "fmap2", torch.float16)
-    _check(coords, "coords")
+    check_operands([(fmap1, "fmap1")], torch.float16); check_operands([(fmap2, "fmap2")], torch.float16)
+    check_operands([(coords, "coords")])
     B, S, H1, W1, _ = coords.shape
     _, H2, W2, C = fmap2.shape
     rd = 2 * radius + 1
     corr = torch.empty((B, S, rd * rd, H1, W1), dtype=torch.float32, device=fmap1.device)
     if B == 0:
         return [corr]
-    with torch.cuda.device(fmap1.device):
-        rc = _lib.load().lgu_altcorr_fwd_h16(_ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr), B, S, H1, W1, H2, W2, C,
-                                             radius, _stream(fmap1))
-    _lib.check(rc, "altcorr_forward_mixed")
+    launch("lgu_altcorr_fwd_h16", "altcorr_forward_mixed", fmap1.device, _ptr(fmap1), _ptr(fmap2), _ptr(coords), _ptr(corr),
+           B, S, H1, W1, H2, W2, C, radius, _stream(fmap1))
     return [corr]
 
 
@@ -320,15 +233,15 @@ class LowmemPyramidPlan:
         if len(offsets) != L or not 1 <= L <= 4:
             raise RuntimeError("LowmemPyramidPlan: need 1..4 levels and one offset entry (tensor or None) per level")
         dt = torch.float16 if fmap1.dtype == torch.float16 else torch.float32
-        _check_dtype(fmap1, "fmap1", dt)
+        check_operands([(fmap1, "fmap1")], dt)
         for l, f in enumerate(fmap2s):
-            _check_dtype(f, "fmap2[%d]" % l, dt)
+            check_operands([(f, "fmap2[%d]" % l)], dt)
             if offsets[l] is not None:
-                _check(offsets[l], "offset[%d]" % l)
+                check_operands([(offsets[l], "offset[%d]" % l)])
         if (ii is None) != (jj is None):
             raise RuntimeError("LowmemPyramidPlan: pass both ii and jj or neither")
         if ii is not None:
-            _check_dtype(ii, "ii", torch.int64); _check_dtype(jj, "jj", torch.int64)
+            check_operands([(ii, "ii")], torch.int64); check_operands([(jj, "jj")], torch.int64)
             if ii.dim() != 1 or ii.shape != jj.shape:
                 raise RuntimeError("LowmemPyramidPlan: ii and jj must be 1-D and of equal length")
         self._keep = (fmap1, list(fmap2s), list(offsets), ii, jj)
@@ -336,7 +249,7 @@ class LowmemPyramidPlan:
         _, self.H1, self.W1, self.C = fmap1.shape
         self.B = fmap1.shape[0] if ii is None else ii.shape[0]
         self.device = fmap1.device
-        self._guard = _CurrentDevice(self.device)
+        self._guard = CurrentDevice(self.device)
         self.NO = max([o.shape[0] for o in offsets if o is not None] or [max(self.B, 1)])
         self._f2 = (_vp * L)(*[f.data_ptr() for f in fmap2s])
         self._op = (_vp * L)(*[(o.data_ptr() if o is not None else None) for o in offsets])
@@ -352,7 +265,7 @@ class LowmemPyramidPlan:
         lib = _lib.load()
         self._rows = None
         if off_row is not None:
-            _check_dtype(off_row, "off_row", torch.int32)
+            check_operands([(off_row, "off_row")], torch.int32)
             if dt != torch.float16 or off_row.dim() != 1 or off_row.shape[0] != self.B or not off_row.is_contiguous():
                 raise RuntimeError("LowmemPyramidPlan: off_row needs half feature maps and one int32 entry per edge")
             rows = {o.shape[0] for o in offsets if o is not None}
@@ -369,7 +282,7 @@ class LowmemPyramidPlan:
             self._fn = lib.lgu_lowmem_pyramid_fwd_h16 if dt == torch.float16 else lib.lgu_lowmem_pyramid_fwd_f32
 
     def __call__(self, coords, out=None):
-        _check(coords, "coords")
+        check_operands([(coords, "coords")])
         B, S, H1, W1, _ = coords.shape
         if (B, H1, W1) != (self.B, self.H1, self.W1):
             raise RuntimeError("coords must be (B,S,H1,W1,2) for the planned feature maps")
@@ -408,7 +321,7 @@ def lowmem_chunked(fmap):
 def lowmem_pyramid_forward_mixed(fmap1, fmap2s, coords, offsets, radius, out=None, ii=None, jj=None, lbase=0, chunked=False,
                                  off_row=None):
     """One-shot form of LowmemPyramidPlan (half or float feature maps)."""
-    with torch.cuda.device(fmap1.device):
+    with CurrentDevice(fmap1.device):
         return LowmemPyramidPlan(fmap1, fmap2s, offsets, radius, ii=ii, jj=jj, lbase=lbase, chunked=chunked,
                                  off_row=off_row)(coords, out=out)
 
@@ -428,7 +341,7 @@ def _pyr_out(out_format, E, C, H1, W1, device, out):
     if out_format == "planar":
         if out is None:
             return torch.empty((E, C, H1, W1), dtype=torch.float32, device=device)
-        _check(out, "out")
+        check_operands([(out, "out")])
         return out
     dt = torch.float16 if out_format == "nhwc_f16" else torch.float32
     if out is None:
@@ -450,7 +363,7 @@ def volume_retile(volume, to_tiled=True, hw=None):
     """Layout conversion of a pyramid level.  to_tiled: (E,H1,W1,H2,W2) row-major slices -> tiled
     (E,H1,W1,ceil(H2/4),ceil(W2/8),4,8) (padding zero-filled).  Otherwise the inverse; `hw` = the logical
     (H2, W2) when the tiled form is padded.  Setup / test utility, not on the lookup path."""
-    _check(volume, "volume")
+    check_operands([(volume, "volume")])
     if to_tiled:
         E, H1, W1, H2, W2 = volume.shape
         out = torch.empty(tiled_shape(E, H1, W1, H2, W2), dtype=volume.dtype, device=volume.device)
@@ -463,9 +376,8 @@ def volume_retile(volume, to_tiled=True, hw=None):
     n = E * H1 * W1
     if n == 0:
         return out
-    with torch.cuda.device(volume.device):
-        rc = _lib.load().lgu_volume_retile_f32(_ptr(volume), _ptr(out), n, H2, W2, 1 if to_tiled else 0, _stream(volume))
-    _lib.check(rc, "volume_retile")
+    launch("lgu_volume_retile_f32", "volume_retile", volume.device, _ptr(volume), _ptr(out), n, H2, W2, 1 if to_tiled else 0,
+           _stream(volume))
     return out
 
 
@@ -497,11 +409,11 @@ def defcorr_pyramid_forward(volumes, coords, offsets, radius, probe=False, out=N
     L = len(volumes)
     if len(offsets) != L:
         raise RuntimeError("defcorr_pyramid_forward: need one offset entry (tensor or None) per level")
-    _check(coords, "coords")
+    check_operands([(coords, "coords")])
     for l, v in enumerate(volumes):
-        _check(v, "volume[%d]" % l)
+        check_operands([(v, "volume[%d]" % l)])
         if offsets[l] is not None:
-            _check(offsets[l], "offset[%d]" % l)
+            check_operands([(offsets[l], "offset[%d]" % l)])
     E, H1, W1 = volumes[0].shape[:3]
     rd = 2 * radius + 1
     hs, ws = _level_dims(volumes, tiled, level_hw)
@@ -516,10 +428,8 @@ def defcorr_pyramid_forward(volumes, coords, offsets, radius, probe=False, out=N
              | OUT_FORMATS[out_format])
     if tuple(coords.shape) != ((E, H1, W1, 2) if coords_last else (E, 2, H1, W1)):
         raise RuntimeError("defcorr_pyramid_forward: coords must be %s" % ("(E,H1,W1,2)" if coords_last else "(E,2,H1,W1)"))
-    with torch.cuda.device(coords.device):
-        rc = _lib.load().lgu_defcorr_pyramid_fwd_f32(vp, _ptr(coords), op, _ptr(out), L, E, H1, W1, h2, w2, radius,
-                                                     flags, _stream(coords))
-    _lib.check(rc, "defcorr_pyramid_forward")
+    launch("lgu_defcorr_pyramid_fwd_f32", "defcorr_pyramid_forward", coords.device, vp, _ptr(coords), op, _ptr(out), L, E,
+           H1, W1, h2, w2, radius, flags, _stream(coords))
     return out
 
 
@@ -536,12 +446,12 @@ def volume_pyramid(means, covs, volume, num_levels, radius=4, inplace=False, til
     gaussianMask_cuda.py:79-86); passing that det reproduces them.  None: det = cov0 * cov1 in fp32."""
     half_in = volume.dtype == torch.float16
     if half_in:
-        _check(means, "means", covs, "covs")
+        check_operands([(means, "means"), (covs, "covs")])
         if not (volume.is_cuda and volume.is_contiguous()):
             raise RuntimeError("volume must be a contiguous CUDA tensor")
         inplace = False
     else:
-        _check(volume, "volume", means, "means", covs, "covs")
+        check_operands([(volume, "volume"), (means, "means"), (covs, "covs")])
     E, H1, W1, H2, W2 = volume.shape
     f32 = torch.float32
     if tiled:
@@ -560,20 +470,16 @@ def volume_pyramid(means, covs, volume, num_levels, radius=4, inplace=False, til
     if det is not None:
         if det.dtype not in (torch.float32, torch.float16) or not (det.is_cuda and det.is_contiguous()) or det.numel() != E * H1 * W1:
             raise RuntimeError("det must be a contiguous fp32 or half CUDA tensor of E*H1*W1 elements")
-        with torch.cuda.device(volume.device):
-            rc = _lib.load().lgu_volume_pyramid_det(_ptr(means), _ptr(covs), _ptr(det), 1 if det.dtype == torch.float16 else 0,
-                                                    _ptr(volume), 1 if half_in else 0, lp, num_levels, E, H1, W1, H2, W2, radius,
-                                                    1 if tiled else 0, _stream(volume))
-        _lib.check(rc, "volume_pyramid")
+        launch("lgu_volume_pyramid_det", "volume_pyramid", volume.device, _ptr(means), _ptr(covs), _ptr(det),
+               1 if det.dtype == torch.float16 else 0, _ptr(volume), 1 if half_in else 0, lp, num_levels, E, H1, W1, H2, W2,
+               radius, 1 if tiled else 0, _stream(volume))
         return levels
-    with torch.cuda.device(volume.device):
-        if half_in:
-            rc = _lib.load().lgu_volume_pyramid_h16(_ptr(means), _ptr(covs), _ptr(volume), lp, num_levels, E, H1, W1, H2, W2,
-                                                    radius, 1 if tiled else 0, _stream(volume))
-        else:
-            fn = _lib.load().lgu_volume_pyramid_tiled_f32 if tiled else _lib.load().lgu_volume_pyramid_f32
-            rc = fn(_ptr(means), _ptr(covs), _ptr(volume), lp, num_levels, E, H1, W1, H2, W2, radius, _stream(volume))
-    _lib.check(rc, "volume_pyramid")
+    if half_in:
+        launch("lgu_volume_pyramid_h16", "volume_pyramid", volume.device, _ptr(means), _ptr(covs), _ptr(volume), lp, num_levels,
+               E, H1, W1, H2, W2, radius, 1 if tiled else 0, _stream(volume))
+    else:
+        launch("lgu_volume_pyramid_tiled_f32" if tiled else "lgu_volume_pyramid_f32", "volume_pyramid", volume.device,
+               _ptr(means), _ptr(covs), _ptr(volume), lp, num_levels, E, H1, W1, H2, W2, radius, _stream(volume))
     return levels
 
 
@@ -591,11 +497,11 @@ def volume_build_pyramid(fmap1, fmap2, means, covs, det=None, num_levels=4, radi
     if half:
         if fmap1.dtype != torch.float16 or not (fmap1.is_cuda and fmap1.is_contiguous()) or fmap1.dim() != 4 or fmap1.shape[3] % 2:
             raise RuntimeError("volume_build_pyramid: the half form takes one contiguous (E,H,W,2C) half CUDA tensor")
-        _check(means, "means", covs, "covs")
+        check_operands([(means, "means"), (covs, "covs")])
         E, H, W, C2 = fmap1.shape
         C = C2 // 2
     else:
-        _check(fmap1, "fmap1", fmap2, "fmap2", means, "means", covs, "covs")
+        check_operands([(fmap1, "fmap1"), (fmap2, "fmap2"), (means, "means"), (covs, "covs")])
         E, C, H, W = fmap1.shape
         if tuple(fmap2.shape) != (E, C, H, W):
             raise RuntimeError("volume_build_pyramid: fmap1 / fmap2 (E,C,H,W)")
@@ -612,15 +518,10 @@ def volume_build_pyramid(fmap1, fmap2, means, covs, det=None, num_levels=4, radi
             raise RuntimeError("det must be a contiguous fp32 or half CUDA tensor of E*H*W elements")
         dptr, dhalf = _ptr(det), 1 if det.dtype == torch.float16 else 0
     lp = (_vp * num_levels)(*[t.data_ptr() for t in levels])
-    with torch.cuda.device(fmap1.device):
-        if half:
-            work = torch.empty_like(fmap1)   # the maps in MFMA fragment order (written by the entry's first launch)
-            rc = _lib.load().lgu_volume_build_pyramid_h16(_ptr(fmap1), _ptr(work), _ptr(means), _ptr(covs), dptr, dhalf, lp,
-                                                          num_levels, E, C, H, W, radius, _stream(fmap1))
-        else:
-            rc = _lib.load().lgu_volume_build_pyramid_f32(_ptr(fmap1), _ptr(fmap2), _ptr(means), _ptr(covs), dptr, dhalf, lp,
-                                                          num_levels, E, C, H, W, radius, _stream(fmap1))
-    _lib.check(rc, "volume_build_pyramid")
+    # half: the second operand is scratch for the maps in MFMA fragment order (written by the entry's first launch)
+    second = torch.empty_like(fmap1) if half else fmap2
+    launch("lgu_volume_build_pyramid_h16" if half else "lgu_volume_build_pyramid_f32", "volume_build_pyramid", fmap1.device,
+           _ptr(fmap1), _ptr(second), _ptr(means), _ptr(covs), dptr, dhalf, lp, num_levels, E, C, H, W, radius, _stream(fmap1))
     return levels
 
 
@@ -640,25 +541,22 @@ def gaussian_params(mean_ofs, cov_raw, h, w, eps=1e-5):
     cov = torch.empty_like(mean)
     det = torch.empty((E, h * w), dtype=mean_ofs.dtype, device=mean_ofs.device)
     if E:
-        with torch.cuda.device(mean.device):
-            rc = _lib.load().lgu_gaussian_params(_ptr(mean_ofs), _ptr(cov_raw), _ptr(mean), _ptr(cov), _ptr(det), E, h, w,
-                                                 1 if mean_ofs.dtype == torch.float16 else 0, float(eps), _stream(mean))
-        _lib.check(rc, "gaussian_params")
+        launch("lgu_gaussian_params", "gaussian_params", mean.device, _ptr(mean_ofs), _ptr(cov_raw), _ptr(mean), _ptr(cov),
+               _ptr(det), E, h, w, 1 if mean_ofs.dtype == torch.float16 else 0, float(eps), _stream(mean))
     return mean, cov, det
 
 
 def probe_mask_scale_(probe, offset):
     """offset *= sigmoid(var(probe over its taps)) in place (reference corr.py:203-207): probe (E,1,T,H,W) or (E,T,H,W)
     fp32 from altcorr_forward / the fused probe launch, offset (E,H,W,C) fp32."""
-    _check(probe, "probe", offset, "offset")
+    check_operands([(probe, "probe"), (offset, "offset")])
     E, H, W, C = offset.shape
     T = probe.numel() // max(E * H * W, 1)
     if probe.numel() != E * T * H * W or T < 2:
         raise RuntimeError("probe_mask_scale_: probe must hold T >= 2 samples per pixel of offset")
     if E:
-        with torch.cuda.device(offset.device):
-            rc = _lib.load().lgu_probe_mask_scale_f32(_ptr(probe), _ptr(offset), E, H * W, T, C, _stream(offset))
-        _lib.check(rc, "probe_mask_scale")
+        launch("lgu_probe_mask_scale_f32", "probe_mask_scale", offset.device, _ptr(probe), _ptr(offset), E, H * W, T, C,
+               _stream(offset))
     return offset
 
 
@@ -702,7 +600,7 @@ class OffsetHeadCache:
 
     def __init__(self, frames, parts, frames_lo=None):
         wa, wb, bias, Cout, C = parts
-        _check_dtype(frames, "frames", torch.float16)
+        check_operands([(frames, "frames")], torch.float16)
         NF, H, W, Cf = frames.shape
         if Cf != C or not frames.is_contiguous():
             raise RuntimeError("OffsetHeadCache: frames must be contiguous (NF,H,W,%d)" % C)
@@ -726,17 +624,16 @@ class OffsetHeadCache:
         """Device-side claim of the frames of ii / jj that have no partials yet -> (worklist, count) tensors.  Two heads
         over the same frames (AltCorrBlock's full-resolution and residual head) share ONE mark pass: the flags of the
         cache that marks stand for both."""
-        _check_dtype(ii, "ii", torch.int64)
-        _check_dtype(jj, "jj", torch.int64)
+        check_operands([(ii, "ii")], torch.int64)
+        check_operands([(jj, "jj")], torch.int64)
         E = ii.shape[0]
         if 2 * E > 65535:   # the worklist convolution sizes its grid with 2E
             raise _lib.UnsupportedShape("OffsetHeadCache: at most 32767 edges per call")
         if self.worklist is None or self.worklist.numel() < 2 * E:
             self.worklist = torch.empty(max(2 * E, 64), dtype=torch.int32, device=self.frames.device)
         if E:
-            with torch.cuda.device(self.frames.device):
-                _lib.check(_lib.load().lgu_offset_heads_mark(_ptr(ii), _ptr(jj), E, _ptr(self.done), self.NF, _ptr(self.worklist),
-                                                             _ptr(self.count), _stream(self.frames)), "offset_heads_mark")
+            launch("lgu_offset_heads_mark", "offset_heads_mark", self.frames.device, _ptr(ii), _ptr(jj), E, _ptr(self.done), self.NF,
+                   _ptr(self.worklist), _ptr(self.count), _stream(self.frames))
         return self.worklist, self.count
 
     def convolve(self, work, E):
@@ -745,10 +642,9 @@ class OffsetHeadCache:
             return
         wa, wb, bias, Cout, C = self.parts
         wl, cnt = work
-        with torch.cuda.device(self.frames.device):
-            _lib.check(_lib.load().lgu_offset_conv_worklist_h16(
-                _ptr(self.frames), _ptr(self.frames_lo) if self.frames_lo is not None else None, _ptr(wl), _ptr(cnt), 2 * E, _ptr(wa),
-                _ptr(wb), _ptr(bias), _ptr(self.PA), _ptr(self.PB), self.H, self.W, C, Cout, _stream(self.frames)), "offset_conv_worklist")
+        launch("lgu_offset_conv_worklist_h16", "offset_conv_worklist", self.frames.device, _ptr(self.frames),
+               _ptr(self.frames_lo) if self.frames_lo is not None else None, _ptr(wl), _ptr(cnt), 2 * E, _ptr(wa), _ptr(wb),
+               _ptr(bias), _ptr(self.PA), _ptr(self.PB), self.H, self.W, C, Cout, _stream(self.frames))
 
     def combine(self, ii, jj, reset=None):
         """(E, Cout, H, W) fp32 = P_A[ii] + P_B[jj]; reset: the count tensor of the mark pass, zeroed by the LAST combine
@@ -756,10 +652,9 @@ class OffsetHeadCache:
         E = ii.shape[0]
         out = torch.empty((E, self.Cout, self.H, self.W), dtype=torch.float32, device=self.frames.device)
         if E:
-            with torch.cuda.device(self.frames.device):
-                _lib.check(_lib.load().lgu_offset_heads_combine_f32(_ptr(self.PA), _ptr(self.PB), _ptr(ii), _ptr(jj), _ptr(out), E,
-                                                                    self.Cout * self.H * self.W, _ptr(reset) if reset is not None else None,
-                                                                    _stream(self.frames)), "offset_heads_combine")
+            launch("lgu_offset_heads_combine_f32", "offset_heads_combine", self.frames.device, _ptr(self.PA), _ptr(self.PB), _ptr(ii),
+                   _ptr(jj), _ptr(out), E, self.Cout * self.H * self.W, _ptr(reset) if reset is not None else None,
+                   _stream(self.frames))
         return out
 
     def __call__(self, ii, jj):
@@ -775,13 +670,13 @@ def offset_conv_frames(frames, ii, jj, packed, frames_lo=None):
     pack_offset_conv.  frames_lo: optional second half part of the input (input = frames + frames_lo, same shape).
     Returns (E, Cout, H, W) fp32."""
     wpack, bias, Cout, C = packed
-    _check_dtype(frames, "frames", torch.float16)
+    check_operands([(frames, "frames")], torch.float16)
     if frames_lo is not None:
-        _check_dtype(frames_lo, "frames_lo", torch.float16)
+        check_operands([(frames_lo, "frames_lo")], torch.float16)
         if frames_lo.shape != frames.shape:
             raise RuntimeError("offset_conv_frames: frames_lo must have the shape of frames")
-    _check_dtype(ii, "ii", torch.int64)
-    _check_dtype(jj, "jj", torch.int64)
+    check_operands([(ii, "ii")], torch.int64)
+    check_operands([(jj, "jj")], torch.int64)
     NF, H, W, Cf = frames.shape
     if Cf != C or not frames.is_contiguous():
         raise RuntimeError("offset_conv_frames: frames must be contiguous (NF,H,W,%d)" % C)
@@ -789,10 +684,9 @@ def offset_conv_frames(frames, ii, jj, packed, frames_lo=None):
     out = torch.empty((E, Cout, H, W), dtype=torch.float32, device=frames.device)
     if E == 0:
         return out
-    with torch.cuda.device(frames.device):
-        rc = _lib.load().lgu_offset_conv_frames_h16(_ptr(frames), _ptr(frames_lo) if frames_lo is not None else None, _ptr(ii),
-                                                    _ptr(jj), _ptr(wpack), _ptr(bias), _ptr(out), E, H, W, C, Cout, _stream(frames))
-    _lib.check(rc, "offset_conv_frames")
+    launch("lgu_offset_conv_frames_h16", "offset_conv_frames", frames.device, _ptr(frames),
+           _ptr(frames_lo) if frames_lo is not None else None, _ptr(ii), _ptr(jj), _ptr(wpack), _ptr(bias), _ptr(out), E, H,
+           W, C, Cout, _stream(frames))
     return out
 
 
@@ -820,21 +714,18 @@ def offsets_finalize(o0, o1_lowres, eps=1e-5, autocast=None, probe=None):
     out1 = torch.empty_like(out0)
     if E == 0:
         return out0, out1
-    lib = _lib.load()
-    scratch = torch.empty(int(lib.lgu_offsets_finalize_scratch_bytes(E)), dtype=torch.uint8, device=o0.device)
+    scratch = torch.empty(int(_lib.load().lgu_offsets_finalize_scratch_bytes(E)), dtype=torch.uint8, device=o0.device)
     mode = (2 if autocast else 1) if o0.dtype == torch.float16 else 0
-    with torch.cuda.device(o0.device):
-        if probe is not None:
-            _check(probe, "probe")
-            T = probe.numel() // max(E * H * W, 1)
-            if probe.numel() != E * T * H * W or T < 2:
-                raise RuntimeError("offsets_finalize: probe must hold T >= 2 samples per pixel")
-            rc = lib.lgu_offsets_finalize_masked(_ptr(o0), _ptr(o1_lowres), _ptr(probe), T, _ptr(out0), _ptr(out1), _ptr(scratch), E, C,
-                                                 H, W, Hl, Wl, mode, float(eps), _stream(o0))
-        else:
-            rc = lib.lgu_offsets_finalize(_ptr(o0), _ptr(o1_lowres), _ptr(out0), _ptr(out1), _ptr(scratch), E, C, H, W, Hl, Wl,
-                                          mode, float(eps), _stream(o0))
-    _lib.check(rc, "offsets_finalize")
+    if probe is not None:
+        check_operands([(probe, "probe")])
+        T = probe.numel() // max(E * H * W, 1)
+        if probe.numel() != E * T * H * W or T < 2:
+            raise RuntimeError("offsets_finalize: probe must hold T >= 2 samples per pixel")
+        launch("lgu_offsets_finalize_masked", "offsets_finalize", o0.device, _ptr(o0), _ptr(o1_lowres), _ptr(probe), T, _ptr(out0),
+               _ptr(out1), _ptr(scratch), E, C, H, W, Hl, Wl, mode, float(eps), _stream(o0))
+    else:
+        launch("lgu_offsets_finalize", "offsets_finalize", o0.device, _ptr(o0), _ptr(o1_lowres), _ptr(out0), _ptr(out1),
+               _ptr(scratch), E, C, H, W, Hl, Wl, mode, float(eps), _stream(o0))
     return out0, out1
 
 
@@ -873,12 +764,12 @@ class DefcorrPyramidPlan:
             raise RuntimeError("DefcorrPyramidPlan: need one offset entry (tensor or None) per level")
         named = []
         for l, v in enumerate(volumes):
-            named += [v, "volume[%d]" % l]
+            named.append((v, "volume[%d]" % l))
             if offsets[l] is not None:
-                named += [offsets[l], "offset[%d]" % l]
-        _check(*named)
+                named.append((offsets[l], "offset[%d]" % l))
+        check_operands(named)
         if slots is not None:
-            _check_dtype(slots, "slots", torch.int32)
+            check_operands([(slots, "slots")], torch.int32)
         self._keep = (list(volumes), list(offsets), slots)  # keep the buffers alive
         self.L, self.radius = L, radius
         if out_format not in OUT_FORMATS:
@@ -902,7 +793,7 @@ class DefcorrPyramidPlan:
             self.E = slots.shape[0]
         self._slots = slots.data_ptr() if slots is not None and slots.numel() else None
         self.device = volumes[0].device
-        self._guard = _CurrentDevice(self.device)
+        self._guard = CurrentDevice(self.device)
         self.channels = L * (2 * radius + 1) ** 2
         self._vp = (_vp * L)(*[v.data_ptr() for v in volumes])
         self._op = (_vp * L)(*[(o.data_ptr() if o is not None else None) for o in offsets])
@@ -916,7 +807,7 @@ class DefcorrPyramidPlan:
         want = (self.E, self.H1, self.W1, 2) if self.coords_last else (self.E, 2, self.H1, self.W1)
         if tuple(coords.shape) != want:
             raise RuntimeError("coords must be %s" % ("(E,H1,W1,2)" if self.coords_last else "(E,2,H1,W1)"))
-        _check(coords, "coords")
+        check_operands([(coords, "coords")])
         out = _pyr_out(self.out_format, self.E, ENC_N if self._enc else self.channels, self.H1, self.W1, self.device, out)
         if self.E == 0:
             return out

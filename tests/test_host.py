@@ -575,3 +575,333 @@ def test_ba_assembly_tables_host_logic():
     assert idx.tolist() == [2, 5, 0, 3, 7, 4]
     ptr, idx = B._csr(np.array([-1, 9]), 3, torch.device("cpu"))
     assert ptr.tolist() == [0, 0, 0, 0] and idx.numel() == 1   # placeholder entry keeps the pointer valid
+
+
+# ---- refusal census: every argument refusal an operator can raise on CPU tensors, its text and its precedence ---------
+_NO_CPU = " must be a HIP device tensor: lgu_slam_amd has no CPU fallback"
+_NO_GRAD = " has no autograd: its outputs would carry no gradient. Call it under torch.no_grad() or pass detached inputs"
+
+
+def _z(*shape, dtype=torch.float32):
+    return torch.zeros(shape, dtype=dtype)
+
+
+def _nc(t):
+    """Same shape and dtype, every stride doubled: not contiguous."""
+    return torch.zeros(tuple(t.shape) + (2,), dtype=t.dtype)[..., 0]
+
+
+def _to(dtype):
+    return lambda t: t.to(dtype)
+
+
+def _as(*shape):
+    return lambda t: torch.zeros(shape, dtype=t.dtype)
+
+
+def _grad(t):
+    return t.requires_grad_()
+
+
+_DBL, _HALF, _INT, _BF16 = _to(torch.float64), _to(torch.float16), _to(torch.int32), _to(torch.bfloat16)
+_L = torch.int64
+
+# operator -> (module, positional tensor arguments in signature order as name -> shape [, dtype], trailing arguments)
+_CENSUS_BASE = {
+    "defCorr_index_forward": ("ops", dict(volume=(1, 2, 2, 4, 4), coords=(1, 2, 2, 2), offset=(1, 2, 2, 3, 3, 2)), (1,)),
+    "defCorr_index_backward": ("ops", dict(volume=(1, 2, 2, 4, 4), coords=(1, 2, 2, 2), offset=(1, 2, 2, 3, 3, 2),
+                                           corr_grad=(1, 3, 3, 2, 2)), (1,)),
+    "corr_index_forward": ("ops", dict(volume=(1, 2, 2, 4, 4), coords=(1, 2, 2, 2)), (1,)),
+    "corr_index_backward": ("ops", dict(volume=(1, 2, 2, 4, 4), coords=(1, 2, 2, 2), corr_grad=(1, 3, 3, 2, 2)), (1,)),
+    "gaussianMask": ("ops", dict(means=(1, 2, 2, 2), covs=(1, 2, 2, 2), volume=(1, 2, 2, 4, 4)), (1,)),
+    "gaussianMask_backward": ("ops", dict(means=(1, 2, 2, 2), covs=(1, 2, 2, 2), volume=(1, 2, 2, 4, 4),
+                                          volume_grad=(1, 2, 2, 4, 4)), (1,)),
+    "lowMem_defSample": ("ops", dict(fmap1=(1, 2, 2, 32), fmap2=(1, 4, 4, 32), coords=(1, 1, 2, 2, 2),
+                                     offset=(1, 2, 2, 3, 3, 2)), (1,)),
+    "altcorr_forward": ("ops", dict(fmap1=(1, 2, 2, 32), fmap2=(1, 4, 4, 32), coords=(1, 1, 2, 2, 2)), (1,)),
+    "altcorr_backward": ("ops", dict(fmap1=(1, 2, 2, 32), fmap2=(1, 4, 4, 32), coords=(1, 1, 2, 2, 2),
+                                     corr_grad=(1, 1, 9, 2, 2)), (1,)),
+    "lowMem_defSample_mixed": ("ops", dict(fmap1=((1, 2, 2, 32), torch.float16), fmap2=((1, 4, 4, 32), torch.float16),
+                                           coords=(1, 1, 2, 2, 2), offset=(1, 2, 2, 3, 3, 2)), (1,)),
+    "altcorr_forward_mixed": ("ops", dict(fmap1=((1, 2, 2, 32), torch.float16), fmap2=((1, 4, 4, 32), torch.float16),
+                                          coords=(1, 1, 2, 2, 2)), (1,)),
+    "frame_distance": ("geom", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(4,), ii=((2,), _L), jj=((2,), _L)), (0.5,)),
+    "projmap": ("geom", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(4,), ii=((2,), _L), jj=((2,), _L)), ()),
+    "depth_filter": ("geom", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(4,), ix=((2,), _L), thresh=(2,)), ()),
+    "iproj": ("geom", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(4,)), ()),
+    "projective_transform": ("geom", dict(poses=(1, 2, 7), disps=(1, 2, 2, 2), intrinsics=(1, 2, 4), ii=((2,), _L),
+                                          jj=((2,), _L)), ()),
+    "reproject": ("geom", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(2, 4), ii=((2,), _L), jj=((2,), _L)), ()),
+    "motion_features": ("geom", dict(poses=(1, 2, 7), disps=(1, 2, 2, 2), intrinsics=(1, 2, 4), ii=((2,), _L), jj=((2,), _L),
+                                     target=(1, 2, 2, 2, 2)), ()),
+    "scatter_mean": ("aggregate", dict(src=(2, 3), index=((3,), _L)), ()),
+    "cvx_upsample": ("aggregate", dict(data=(1, 2, 2, 1), mask=(1, 576, 2, 2)), ()),
+    "upsample_disp": ("aggregate", dict(disp=(1, 1, 2, 2), mask=(1, 1, 576, 2, 2)), ()),
+    "upsample_disps_": ("aggregate", dict(disps_up=(2, 16, 16), disps=(2, 2, 2), ix=((2,), _L), mask=(2, 576, 2, 2)), ()),
+    "kangru_context": ("gru", dict(net=(1, 128, 1, 1), weight=(128, 128), bias=(128,)), ()),
+    "kan_heads": ("gru", dict(glo=(1, 128), grid=(3, 128, 10), wpack=(384, 896)), ()),
+    "kangru_gates_": ("gru", dict(net_inp=(1, 448, 1, 1), cz=(1, 128, 1, 1), cr=(1, 128, 1, 1), kz=(1, 128), kr=(1, 128),
+                                  net=(1, 128, 1, 1)), ()),
+    "kangru_blend": ("gru", dict(cq=(1, 128, 1, 1), kq=(1, 128), z=(1, 128, 1, 1), net=(1, 128, 1, 1)), ()),
+    "instance_norm_relu": ("features", dict(a=(1, 1, 2, 2)), ()),
+    "normalize_images": ("features", dict(image=((1, 3, 2, 2), torch.uint8)), ()),
+    "flow_conv7_relu": ("flow", dict(x=(1, 4, 1, 1), wpack=((7, 8, 64, 8), torch.float16), bias_h=((128,), torch.float16)), ()),
+    # t = 2, t0 = t1 = 0: a window of n = 4 cells
+    "proximity_edges": ("graph", dict(poses=(2, 7), disps=(2, 2, 2), intrinsics=(4,), t=None, ii_known=((2,), _L),
+                                      jj_known=((2,), _L)), ()),
+}
+
+
+def _census_cases():
+    """(operator, edits of the valid CPU call, keyword arguments, exception, message).  An edit maps an argument name to a
+    function of its valid tensor; every unedited call would be refused only for living on the CPU."""
+    R, V, N, I = RuntimeError, ValueError, NotImplementedError, IndexError
+    c = []
+
+    def add(op, edits, exc, msg, **kw):
+        c.append((op, edits, kw, exc, msg))
+
+    # -- ops: contiguity of every argument, then per argument HIP device and dtype; shapes only after those ------------
+    for op, first, second, last in (("defCorr_index_forward", "volume", "coords", "offset"),
+                                    ("defCorr_index_backward", "volume", "coords", "corr_grad"),
+                                    ("corr_index_forward", "volume", "coords", "coords"),
+                                    ("corr_index_backward", "volume", "coords", "corr_grad"),
+                                    ("gaussianMask", "volume", "means", "covs"),
+                                    ("gaussianMask_backward", "volume", "means", "volume_grad"),
+                                    ("lowMem_defSample", "fmap1", "fmap2", "offset"),
+                                    ("altcorr_forward", "fmap1", "fmap2", "coords"),
+                                    ("altcorr_backward", "fmap1", "fmap2", "corr_grad")):
+        add(op, {}, R, first + _NO_CPU)
+        add(op, {last: _nc}, R, last + " must be contiguous")
+        add(op, {first: _nc, second: _nc}, R, first + " must be contiguous")       # two defects: the order of the checks
+        add(op, {first: _BF16, last: _nc}, R, last + " must be contiguous")        # contiguity before device and dtype
+        add(op, {first: _BF16}, R, first + _NO_CPU)                                # device before dtype
+    for op in ("lowMem_defSample_mixed", "altcorr_forward_mixed"):
+        add(op, {}, R, "fmap1" + _NO_CPU)
+        add(op, {"fmap1": _nc}, R, "fmap1 must be contiguous")
+        add(op, {"fmap2": _nc}, R, "fmap1" + _NO_CPU)                              # two defects: fmap1 is checked whole first
+        add(op, {"fmap1": _to(torch.float32)}, R, "fmap1" + _NO_CPU)
+    # half / double volumes: every scalar operand has the volume's dtype, coords stays float; contiguity first
+    add("defCorr_index_forward", {"volume": _HALF}, R, "expected scalar type Half but found Float")
+    add("defCorr_index_forward", {"volume": _HALF, "offset": _HALF, "coords": _DBL}, R, "expected scalar type Float but found Double")
+    add("defCorr_index_forward", {"volume": _HALF, "coords": _DBL}, R, "expected scalar type Float but found Double")
+    add("defCorr_index_forward", {"volume": _HALF, "coords": _DBL, "offset": _nc}, R, "offset must be contiguous")
+    add("defCorr_index_forward", {"volume": _HALF, "coords": _nc, "offset": _nc}, R, "offset must be contiguous")
+    add("defCorr_index_forward", {"volume": _HALF, "offset": _HALF}, R, "volume" + _NO_CPU)
+    add("defCorr_index_backward", {"volume": _DBL, "offset": _DBL}, R, "expected scalar type Double but found Float")
+    add("defCorr_index_backward", {"volume": _DBL, "corr_grad": _nc}, R, "corr_grad must be contiguous")
+    add("corr_index_forward", {"volume": _HALF, "coords": _HALF}, R, "expected scalar type Float but found Half")
+    add("corr_index_forward", {"volume": _HALF, "coords": _nc}, R, "coords must be contiguous")
+    add("corr_index_backward", {"volume": _HALF}, R, "expected scalar type Half but found Float")
+    add("corr_index_backward", {"volume": _HALF, "coords": _INT}, R, "expected scalar type Float but found Int")
+    add("gaussianMask", {"volume": _DBL, "means": _DBL}, R, "expected scalar type Double but found Float")
+    add("gaussianMask", {"volume": _HALF, "means": _nc}, R, "means must be contiguous")
+    add("gaussianMask_backward", {"volume": _HALF, "means": _HALF, "covs": _HALF, "volume_grad": _to(torch.int8)}, R,
+        "expected scalar type Half but found torch.int8")
+    add("gaussianMask_backward", {"volume": _HALF, "covs": _nc}, R, "covs must be contiguous")
+
+    # -- geom: contiguity, dtypes, shapes, no-grad, device ---------------------------------------------------------------
+    for op in ("frame_distance", "projmap", "depth_filter", "iproj", "projective_transform", "reproject", "motion_features"):
+        ix = "ix" if op == "depth_filter" else "ii"
+        add(op, {}, R, "poses" + _NO_CPU)
+        add(op, {"disps": _nc}, R, "disps must be contiguous")
+        add(op, {"disps": _DBL}, R, "expected scalar type Float but found Double (disps)")
+        add(op, {"intrinsics": _to(torch.int8)}, R, "expected scalar type Float but found torch.int8 (intrinsics)")
+        add(op, {"poses": _HALF, "intrinsics": _nc}, R, "intrinsics must be contiguous")       # two defects
+        if op != "iproj":
+            add(op, {ix: _INT}, R, "expected scalar type Long but found Int (%s)" % ix)
+            add(op, {"intrinsics": _DBL, ix: _nc}, R, ix + " must be contiguous")              # two defects
+    for op in ("frame_distance", "projmap", "depth_filter", "iproj"):
+        add(op, {"poses": _as(2, 6)}, R, "poses must be (N,7) = t, q(xyzw), got (2, 6)")
+        add(op, {"disps": _as(2, 2)}, R, "disps must be (N,ht,wd), got (2, 2)")
+        add(op, {"intrinsics": _as(3)}, R, "intrinsics must be 1-D with fx, fy, cx, cy, got (3,)")
+        add(op, {"poses": _as(2, 6), "disps": _DBL}, R, "expected scalar type Float but found Double (disps)")  # two defects
+    for op in ("frame_distance", "projmap"):
+        add(op, {"jj": _as(3)}, R, "ii and jj must be 1-D and of equal length, got (2,) and (3,)")
+        add(op, {"jj": _as(3), "intrinsics": _as(3)}, R, "intrinsics must be 1-D with fx, fy, cx, cy, got (3,)")
+    add("depth_filter", {"ix": _as(2, 1)}, R, "ix must be 1-D, got (2, 1)")
+    add("depth_filter", {"thresh": _as(1)}, R, "thresh must be 1-D with one entry per index of ix (2), got (1,)")
+    add("depth_filter", {"thresh": _DBL}, R, "expected scalar type Float but found Double (thresh)")
+    add("depth_filter", {"thresh": _DBL, "ix": _INT}, R, "expected scalar type Long but found Int (ix)")
+    for op in ("projective_transform", "motion_features"):
+        add(op, {"poses": _as(2, 7)}, R, "poses must be (B,N,7) = t, q(xyzw), got (2, 7)")
+        add(op, {"disps": _as(2, 2, 2)}, R, "disps must be (B,N,ht,wd), got (2, 2, 2)")
+        add(op, {"intrinsics": _as(1, 2, 3)}, R, "intrinsics must be (B,N,4) = fx, fy, cx, cy per frame, got (1, 2, 3)")
+        add(op, {"disps": _as(2, 2, 2, 2)}, R, "poses, disps and intrinsics must have the same batch size, got 1, 2 and 1")
+        add(op, {"jj": _as(2, 1)}, R, "ii and jj must be 1-D and of equal length, got (2,) and (2, 1)")
+        add(op, {"disps": _grad}, R, op + _NO_GRAD)
+        add(op, {"disps": _grad, "jj": _as(3)}, R, "ii and jj must be 1-D and of equal length, got (2,) and (3,)")
+    add("reproject", {"poses": _as(2, 6)}, R, "poses must be (B,N,7) = t, q(xyzw), got (1, 2, 6)")
+    add("reproject", {"intrinsics": _grad}, R, "projective_transform" + _NO_GRAD)
+    add("reproject", {"intrinsics": _grad, "ii": _INT}, R, "expected scalar type Long but found Int (ii)")
+    add("motion_features", {"target": _as(1, 2, 2, 2, 3)}, R, "target must be (B,E,ht,wd,2) = (1, 2, 2, 2, 2), got (1, 2, 2, 2, 3)")
+    add("motion_features", {"target": _DBL}, R, "expected scalar type Float but found Double (target)")
+    add("motion_features", {"target": _nc}, R, "target must be contiguous")
+    add("motion_features", {"target": lambda t: torch.zeros((1, 2, 2, 2, 3), dtype=torch.float64)}, R,
+        "expected scalar type Float but found Double (target)")
+    add("motion_features", {}, R, "clamp must be a non-negative bound, got -1.0", clamp=-1.0)
+    add("motion_features", {"target": _grad}, R, "clamp must be a non-negative bound, got -1.0", clamp=-1.0)
+    add("motion_features", {"target": _grad}, R, "motion_features" + _NO_GRAD)
+
+    # -- aggregate ----------------------------------------------------------------------------------------------------------
+    add("scatter_mean", {}, R, "src" + _NO_CPU)
+    add("scatter_mean", {}, N, "scatter_mean: only out=None is supported (the reference's call form scatter_mean(src, index, "
+        "dim=d) with a 1-D index of length src.size(d))", out=_z(2, 3))
+    add("scatter_mean", {}, I, "dim 2 out of range for a 2-D src", dim=2)
+    add("scatter_mean", {"index": _as(2)}, N, "scatter_mean: only a 1-D index of length src.size(dim) = 3 is supported (the "
+        "reference's call form), got index of shape (2,)")
+    add("scatter_mean", {"src": _nc}, R, "src must be contiguous")
+    add("scatter_mean", {"src": _DBL}, R, "expected scalar type Float or Half but found Double (src)")
+    add("scatter_mean", {"src": _to(torch.uint8)}, R, "expected scalar type Float or Half but found torch.uint8 (src)")
+    add("scatter_mean", {"index": _INT}, R, "expected scalar type Long but found Int (index)")
+    add("scatter_mean", {}, R, "dim_size must be >= 0, got -1", dim_size=-1)
+    add("scatter_mean", {"src": _grad}, R, "scatter_mean" + _NO_GRAD)
+    add("scatter_mean", {"src": _HALF}, R, "src" + _NO_CPU)
+    add("scatter_mean", {"src": _DBL, "index": _nc}, R, "index must be contiguous")            # two defects
+    add("scatter_mean", {"src": _grad, "index": _INT}, R, "expected scalar type Long but found Int (index)")
+    add("cvx_upsample", {}, R, "data" + _NO_CPU)
+    add("cvx_upsample", {"data": _as(1, 2, 2)}, R, "data must be (B,ht,wd,dim), got (1, 2, 2)")
+    add("cvx_upsample", {"data": _as(1, 2, 2, 2)}, N, "cvx_upsample: only data width 1 (the disparity) is supported, got 2")
+    add("cvx_upsample", {"mask": _nc}, R, "mask must be contiguous")
+    add("cvx_upsample", {"data": _HALF}, R, "expected scalar type Float but found Half (data)")
+    add("cvx_upsample", {"mask": _as(1, 575, 2, 2)}, R, "mask must be (1,576,2,2), optionally with leading 1s, got (1, 575, 2, 2)")
+    add("cvx_upsample", {"mask": _DBL}, R, "expected scalar type Float or Half but found Double (mask)")
+    add("cvx_upsample", {"mask": _grad}, R, "cvx_upsample" + _NO_GRAD)
+    add("cvx_upsample", {"mask": _as(1, 1, 576, 2, 2)}, R, "data" + _NO_CPU)                   # leading 1s are accepted
+    add("cvx_upsample", {"data": _DBL, "mask": _as(1, 575, 2, 2)}, R, "expected scalar type Float but found Double (data)")
+    add("cvx_upsample", {"mask": lambda t: torch.zeros((1, 575, 2, 2), dtype=torch.float64)}, R,
+        "mask must be (1,576,2,2), optionally with leading 1s, got (1, 575, 2, 2)")
+    add("upsample_disp", {}, R, "data" + _NO_CPU)
+    add("upsample_disp", {"disp": _as(1, 2, 2)}, R, "disp must be (batch,num,ht,wd), got (1, 2, 2)")
+    add("upsample_disp", {"disp": _nc}, R, "disp must be contiguous")
+    add("upsample_disp", {"mask": _as(1, 1, 575, 2, 2)}, R, "mask must be (1,1,576,2,2), got (1, 1, 575, 2, 2)")
+    add("upsample_disp", {"disp": _DBL}, R, "expected scalar type Float but found Double (data)")
+    add("upsample_disp", {"disp": _grad}, R, "cvx_upsample" + _NO_GRAD)
+    add("upsample_disp", {"mask": lambda t: _nc(torch.zeros(1, 1, 575, 2, 2))}, R, "mask must be contiguous")   # two defects
+    add("upsample_disps_", {}, R, "disps_up" + _NO_CPU)
+    add("upsample_disps_", {"disps": _as(2, 2)}, R, "disps must be (N,ht,wd), got (2, 2)")
+    add("upsample_disps_", {"disps_up": _as(2, 16, 15)}, R, "disps_up must be (N,8ht,8wd) = (2, 16, 16), got (2, 16, 15)")
+    add("upsample_disps_", {"ix": _as(2, 1)}, R, "ix must be 1-D, got (2, 1)")
+    add("upsample_disps_", {"mask": _nc}, R, "mask must be contiguous")
+    add("upsample_disps_", {"disps_up": _DBL}, R, "expected scalar type Float but found Double (disps_up)")
+    add("upsample_disps_", {"disps": _HALF}, R, "expected scalar type Float but found Half (disps)")
+    add("upsample_disps_", {"ix": _INT}, R, "expected scalar type Long but found Int (ix)")
+    add("upsample_disps_", {"mask": _as(3, 576, 2, 2)}, R, "mask must be (2,576,2,2), optionally with leading 1s, got (3, 576, 2, 2)")
+    add("upsample_disps_", {"mask": _BF16}, R, "expected scalar type Float or Half but found BFloat16 (mask)")
+    add("upsample_disps_", {"mask": _grad}, R, "upsample_disps_" + _NO_GRAD)
+    add("upsample_disps_", {"disps": _nc, "ix": _as(2, 1)}, R, "ix must be 1-D, got (2, 1)")   # two defects: shapes first
+    add("upsample_disps_", {"ix": _INT, "mask": _as(3, 576, 2, 2)}, R, "expected scalar type Long but found Int (ix)")
+
+    # -- gru: shapes, contiguity, dtypes (the first operand's), no-grad, device ------------------------------------------
+    for op, first, shaped, two in (("kangru_context", "net", "bias", "weight"), ("kan_heads", "glo", "grid", "wpack"),
+                                   ("kangru_gates_", "net_inp", "kr", "net"), ("kangru_blend", "cq", "kq", "net")):
+        shape = _CENSUS_BASE[op][1][shaped]
+        bad = shape[:-1] + (shape[-1] + 1,)
+        add(op, {}, R, first + _NO_CPU)
+        add(op, {shaped: _as(*bad)}, R, "%s must be %s, got %s" % (shaped, shape, bad))
+        add(op, {two: _nc}, R, two + " must be contiguous")
+        add(op, {first: _DBL}, R, "expected scalar type Float or Half but found Double (%s)" % first)
+        add(op, {two: _HALF}, R, "expected scalar type Float but found Half (%s)" % two)
+        add(op, {two: _grad}, R, op + _NO_GRAD)
+        add(op, {first: _nc, shaped: _as(*bad)}, R, "%s must be %s, got %s" % (shaped, shape, bad))   # two defects
+        add(op, {first: _nc, two: _HALF}, R, first + " must be contiguous")
+        add(op, {first: _HALF, two: _grad}, R, "expected scalar type Half but found Float (%s)"
+            % ("wpack" if op == "kan_heads" else list(_CENSUS_BASE[op][1])[1]))
+    add("kangru_context", {"net": _as(1, 127, 1, 1)}, R, "net must be (E,128,H,W), got (1, 127, 1, 1)")
+    add("kangru_context", {"weight": _as(128, 128, 1, 2)}, R, "weight must be (128, 128, 1, 1), got (128, 128, 1, 2)")
+    add("kangru_context", {"weight": _as(128, 127)}, R, "weight must be (128, 128), got (128, 127)")
+    add("kan_heads", {"glo": _as(1, 127)}, R, "glo must be (E,128), got (1, 127)")
+    add("kan_heads", {"grid": _DBL}, R, "expected scalar type Float but found Double (grid)")
+    add("kan_heads", {"grid": _DBL, "wpack": _HALF}, R, "expected scalar type Float but found Half (wpack)")
+    add("kangru_gates_", {"net_inp": _as(1, 447, 1, 1)}, R, "net_inp must be (E,448,H,W), got (1, 447, 1, 1)")
+    add("kangru_gates_", {"cz": _as(1, 128, 1, 2), "kz": _as(2, 128)}, R, "cz must be (1, 128, 1, 1), got (1, 128, 1, 2)")
+    add("kangru_blend", {"cq": _as(1, 128, 1)}, R, "cq must be (E,128,H,W), got (1, 128, 1)")
+    add("kangru_blend", {"z": _as(2, 128, 1, 1)}, R, "z must be (1, 128, 1, 1), got (2, 128, 1, 1)")
+
+    # -- features ---------------------------------------------------------------------------------------------------------
+    op = "instance_norm_relu"
+    add(op, {}, R, "a" + _NO_CPU)
+    add(op, {"a": _as(1, 2, 2)}, R, "a must be (N,C,H,W), got (1, 2, 2)")
+    add(op, {"a": _DBL}, R, "expected scalar type Float or Half but found Double (a)")
+    add(op, {}, V, "norm_residual=True needs a residual", norm_residual=True)
+    add(op, {}, V, "relu=False is served without a residual only", residual=_z(1, 1, 2, 2), relu=False)
+    add(op, {}, R, "residual must be (1, 1, 2, 2), got (1, 1, 2, 3)", residual=_z(1, 1, 2, 3))
+    add(op, {}, R, "expected scalar type Float but found Half (residual)", residual=_z(1, 1, 2, 2, dtype=torch.float16))
+    add(op, {}, R, "out must be (1, 1, 2, 2), got (1, 1, 3, 2)", out=_z(1, 1, 3, 2))
+    add(op, {"a": _as(1, 1, 1, 1)}, V, "Expected more than 1 spatial element when training, got input size torch.Size([1, 1, 1, 1])")
+    add(op, {}, V, "eps must be >= 0, got -1.0", eps=-1.0)
+    add(op, {"a": _nc}, R, "a must be contiguous")
+    add(op, {}, R, "residual must be contiguous", residual=_nc(_z(1, 1, 2, 2)))
+    add(op, {"a": _grad}, R, op + _NO_GRAD)
+    add(op, {"a": _HALF}, R, "a" + _NO_CPU)
+    add(op, {}, R, "expected scalar type Float but found Half (residual)", residual=_z(1, 1, 2, 2, dtype=torch.float16),
+        out=_z(1, 1, 3, 2))                                                                    # two defects: per tensor
+    add(op, {}, R, "residual must be (1, 1, 2, 2), got (1, 1, 2, 3)", residual=_z(1, 1, 2, 3, dtype=torch.float16))
+    add(op, {"a": lambda t: _nc(t).requires_grad_()}, R, "a must be contiguous")
+    add(op, {"a": _nc}, V, "eps must be >= 0, got -1.0", eps=-1.0)
+    op = "normalize_images"
+    add(op, {"image": _as(1, 2, 2, 2)}, R, "image must be (N,3,H,W), got (1, 2, 2, 2)")
+    add(op, {"image": _to(torch.float32)}, R, "expected scalar type Byte but found Float (image)")
+    add(op, {"image": _to(torch.int8)}, R, "expected scalar type Byte but found torch.int8 (image)")
+    add(op, {}, R, "mean and std must have 3 entries", mean=(0.5, 0.5))
+    add(op, {"image": lambda t: torch.zeros(1, 2, 2, 2)}, R, "image must be (N,3,H,W), got (1, 2, 2, 2)")    # two defects
+    add(op, {"image": _to(torch.float32)}, R, "expected scalar type Byte but found Float (image)", std=(1.0,))
+
+    # -- flow -------------------------------------------------------------------------------------------------------------
+    op = "flow_conv7_relu"
+    add(op, {}, R, "x" + _NO_CPU)
+    add(op, {"x": _as(1, 3, 1, 1)}, R, "x must be (N,4,H,W), got (1, 3, 1, 1)")
+    add(op, {"wpack": _as(7, 8, 64, 7)}, R, "wpack must hold 28672 halves (pack_conv7), got (7, 8, 64, 7)")
+    add(op, {"bias_h": _as(127)}, R, "bias_h must be (128,), got (127,)")
+    add(op, {"x": _nc}, R, "x must be contiguous")
+    add(op, {"x": _DBL}, R, "expected scalar type Float or Half but found Double (x)")
+    add(op, {"wpack": _to(torch.float32)}, R, "expected scalar type Half but found Float (wpack)")
+    add(op, {"bias_h": _BF16}, R, "expected scalar type Half but found BFloat16 (bias_h)")
+    add(op, {"x": _grad}, R, op + _NO_GRAD)
+    add(op, {"x": _HALF}, R, "x" + _NO_CPU)
+    add(op, {"wpack": _to(torch.float32), "bias_h": _nc}, R, "bias_h must be contiguous")      # two defects
+    add(op, {"x": _nc, "bias_h": _as(127)}, R, "bias_h must be (128,), got (127,)")
+    add(op, {"x": _grad, "bias_h": _to(torch.float32)}, R, "expected scalar type Half but found Float (bias_h)")
+
+    # -- graph: contiguity and dtype per tensor in sequence, then shapes, then device ----------------------------------------
+    op = "proximity_edges"
+    add(op, {}, R, "poses" + _NO_CPU)
+    add(op, {"disps": _nc}, R, "disps must be contiguous")
+    add(op, {"disps": _DBL}, R, "expected scalar type Float but found Double (disps)")
+    add(op, {"jj_known": _INT}, R, "expected scalar type Long but found Int (jj_known)")
+    add(op, {"poses": _as(2, 6)}, R, "poses must be (N,7) = t, q(xyzw), got (2, 6)")
+    add(op, {"jj_known": _as(3)}, R, "ii_known and jj_known must be 1-D and of equal length, got (2,) and (3,)")
+    add(op, {"jj_known": lambda t: None}, R, "ii_known and jj_known must both be given or both be None")
+    add(op, {"t": lambda t: 2.5}, R, "proximity_edges: t must be an integer, got 2.5")
+    add(op, {}, R, "proximity_edges: form must be None, 'small' or 'sorted', got 'large'", form="large")
+    add(op, {}, R, "dist" + _NO_CPU, dist=_z(4))
+    add(op, {}, R, "dist must be 1-D with one value per cell (4), got (3,)", dist=_z(3))
+    add(op, {}, R, "expected scalar type Float but found Double (dist)", dist=_z(4, dtype=torch.float64))
+    add(op, {"poses": _DBL, "disps": _nc}, R, "expected scalar type Float but found Double (poses)")   # two defects: per tensor
+    add(op, {"disps": lambda t: _nc(t.double())}, R, "disps must be contiguous")
+    add(op, {"poses": _as(2, 6), "ii_known": _INT}, R, "expected scalar type Long but found Int (ii_known)")
+    add(op, {"poses": _as(2, 6), "jj_known": _as(3)}, R, "ii_known and jj_known must be 1-D and of equal length, got (2,) and (3,)")
+    return [pytest.param(*case, id="%s-%d" % (case[0], n)) for n, case in enumerate(c)]
+
+
+@pytest.mark.parametrize("op,edits,kwargs,exc,message", _census_cases())
+def test_refusal_census(lgu, op, edits, kwargs, exc, message):
+    """Each operator's argument refusals on CPU tensors: the exception type, the whole message and, where a call has two
+    defects, which one is reported.  None of them touches a device."""
+    module, base, tail = _CENSUS_BASE[op]
+    args = []
+    for name, spec in base.items():
+        if spec is None:
+            value = 2                                            # proximity_edges' frame count t
+        else:
+            shape, dtype = spec if isinstance(spec[0], tuple) else (spec, torch.float32)
+            value = torch.zeros(shape, dtype=dtype)
+        args.append(edits[name](value) if name in edits else value)
+    assert not set(edits) - set(base)
+    with pytest.raises(exc) as info:
+        getattr(getattr(lgu, module), op)(*args, *tail, **kwargs)
+    assert type(info.value) is exc and str(info.value) == message
+
+
+def test_refusal_census_covers_every_operator():
+    assert {case.values[0] for case in _census_cases()} == set(_CENSUS_BASE) and len(_census_cases()) == 307
