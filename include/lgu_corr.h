@@ -757,6 +757,39 @@ typedef struct {
 } lgu_flow_conv7_args;
 int lgu_flow_conv7_relu_h16(lgu_flow_conv7_args args, void* stream);
 
+/* ---- update operator: Conv2d(128, 64 | 128, 3, padding=1) + bias (+ ReLU) under float16 autocast (csrc/conv3.hip) ---------
+ * Reference droid_slam/droid_net.py: corr_encoder[2], flow_encoder[2], delta[0], weight[0], GraphAgg.conv1 / conv2.
+ * x (N,128,H,W) NCHW contiguous, float32, or IEEE half with LGU_CONV3_X_HALF; out (N,Cout,H,W) IEEE half, NCHW contiguous,
+ * fully written and nothing outside it; Cout 64 or 128.  Rounding points:
+ *   x_h = half(x), w_h = half(weight), b_h = half(bias)     round to nearest even (x_h in the kernel, and a half x is used
+ *                                                           as it is; the others in the pack)
+ *   s   = b_h + sum over c, ky, kx of x_h[c][y+ky-1][x+kx-1] * w_h[co][c][ky][kx]
+ *                                                           exact half x half products, fp32 accumulation, zero padding
+ *   y   = act(half(s))                                      ONE rounding; act = relu with LGU_CONV3_RELU (a NaN is kept),
+ *                                                           the identity otherwise
+ * The accumulator starts at b_h and takes its 36 K steps in a fixed order (ky, kx, then channel blocks of 32), whatever
+ * the tile: the bits of an image depend on that image, H and W only, not on N or on its position in the batch.  A NaN or
+ * infinite input reaches exactly its 3x3 neighbourhood.  No atomics, no workspace, no host synchronisation.
+ * wpack: LGU_CONV3_WPACK_HALVES_<Cout> halves laid out [9 taps t = 3 ky + kx][4 channel blocks kc][Cout/16 channel tiles
+ *   ct][64 lanes l][8 halves j], the B operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is
+ *   w_h[16 ct + (l & 15)][32 kc + 8 (l >> 4) + j][t / 3][t % 3].  Every slot holds a weight.  16-byte aligned, otherwise
+ *   LGU_E_UNSUPPORTED.  bias: Cout halves b_h.
+ * x, bias and out are served at the alignment of their element with the same bits: out is stored 16 bytes at a time
+ *   where W % 8 == 0 and out is 16-byte aligned, by element otherwise.
+ * Every N >= 0, H >= 1, W >= 1 is served; N == 0 launches nothing.  N < 0, H < 1, W < 1, an unknown flag, a null operand
+ * or one below its element's alignment: LGU_E_BADARG; Cout outside {64, 128}, or more than INT_MAX workgroups (N * the
+ * smaller of ceil(W / 64) * ceil(H / 2) and ceil(W / 32) * ceil(H / 4) by padded area): LGU_E_UNSUPPORTED, nothing written.
+ * The operands travel in one parameter block passed by value. */
+#define LGU_CONV3_WPACK_HALVES_128 147456
+#define LGU_CONV3_WPACK_HALVES_64 73728
+#define LGU_CONV3_X_HALF 1   /* flags: x holds IEEE half */
+#define LGU_CONV3_RELU 2     /* flags: act = relu */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;   /* bias: Cout halves */
+  int N, H, W, Cout, flags;
+} lgu_conv3_args;
+int lgu_conv3x3_c128_h16(lgu_conv3_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

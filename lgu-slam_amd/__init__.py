@@ -10,7 +10,8 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, encoder, features, flow, geom, graph, gru, lie, ops, sharded  # noqa: F401
+from . import _build, _lib, aggregate, ba, conv3, encoder, features, flow, geom, graph, gru, lie, ops, sharded  # noqa: F401
+from .conv3 import Conv3, Conv3Stack  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401

@@ -19,6 +19,12 @@ class FlowConv7Args(ctypes.Structure):
     _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int)]
 
 
+class Conv3Args(ctypes.Structure):
+    """lgu_conv3_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int),
+                ("Cout", _int), ("flags", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -131,6 +137,8 @@ SIGNATURES = {
     "lgu_image_normalize_u8": [_vp, _vp, ctypes.c_long, ctypes.c_long, _c_float_p, _c_float_p, _vp],
     # motion encoder: {x, wpack, bias, out, N, H, W} by value, stream
     "lgu_flow_conv7_relu_h16": [FlowConv7Args, _vp],
+    # 3x3 convolution, 128 in: {x, wpack, bias, out, N, H, W, Cout, flags} by value, stream
+    "lgu_conv3x3_c128_h16": [Conv3Args, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],
