@@ -790,6 +790,58 @@ typedef struct {
 } lgu_conv3_args;
 int lgu_conv3x3_c128_h16(lgu_conv3_args args, void* stream);
 
+/* ---- KAN-bias GRU: Conv2d(448, 128, 3, padding=1) x 3 with the gates and the blend, float16 autocast (csrc/gruconv.hip) ------
+ * Reference droid_slam/modules/gru_kanBias.py: convz, convr, convq of KAN_bias_GRU(128, 320).  All tensors IEEE half.
+ * Input: nseg (1..4) NCHW-contiguous tensors seg[i] (N,seg_ch[i],H,W), read as their concatenation along the channels
+ * without that tensor existing; every seg_ch[i] a multiple of 32, their sum 448.  The split does not change a bit: one
+ * segment of 448, [128,320] and [128,128,128,64] give the same output.  Rounding points:
+ *   w_h = half(weight), b_h = half(bias)                    round to nearest even, in the pack
+ *   s   = b_h + sum over c, ky, kx of x[c][y+ky-1][x+kx-1] * w_h[co][c][ky][kx]
+ *                                                           exact half x half products, fp32 accumulation, zero padding
+ *   c   = half(s)                                           ONE rounding, then by mode (r(v) = half(v) below):
+ *   LGU_GRUCONV_PLAIN  Cout 128 or 256: out0 (N,Cout,H,W) = c.
+ *   LGU_GRUCONV_ZR     Cout 256, the pack's outputs 0..127 convz, 128..255 convr; k0 = kz, k1 = kr (N,128), net (N,128,H,W):
+ *                      out0 = z = r(sigmoid(r(c_z + kz))), out1 = rnet = r(r(sigmoid(r(c_r + kr))) * net), both
+ *                      (N,128,H,W): the arithmetic of lgu_kangru_gates_h16 on c.
+ *   LGU_GRUCONV_Q      Cout 128 (segment 0 is rnet); k0 = kq (N,128), z and net (N,128,H,W):
+ *                      out0 = r(r(r(1 - z) * net) + r(z * r(tanh(r(c + kq))))): the arithmetic of lgu_kangru_blend_h16 on c.
+ * The accumulator starts at b_h and takes its 126 K steps in ONE order, whatever the mode, the tile, N or the segment split:
+ *   step = (c64 * 9 + t) * 2 + kc   c64 < 7: chunk of 64 channels; t = 3 ky + kx < 9: tap; kc < 2: block of 32 channels
+ * covering channels 64 c64 + 32 kc .. + 32 of tap t.  The bits of an image depend on that image, H and W only, not on N
+ * or on its position in the batch.  A NaN or infinite input reaches exactly its 3x3 neighbourhood.  No atomics, no
+ * workspace, no host synchronisation.
+ * wpack: LGU_GRUCONV_WPACK_HALVES_<Cout> halves laid out [126 steps][Cout/16 channel tiles ct][64 lanes l][8 halves j], the
+ *   B operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l in step (c64, t, kc) is
+ *   w_h[16 ct + (l & 15)][64 c64 + 32 kc + 8 (l >> 4) + j][t / 3][t % 3].  Every slot holds a weight.  16-byte aligned,
+ *   otherwise LGU_E_UNSUPPORTED.  bias: Cout halves b_h.
+ * Outputs are fully written and nothing outside them.  They must not overlap any input (other workgroups read the
+ * segments' pixels as halo): rnet is a tensor of its own, never segment 0 of the same call.
+ * Alignment: segments, bias, k0, k1, net, z and the outputs at element alignment (stores and the reads of net and z go
+ * 16 bytes at a time when W % 8 == 0 and the mode's outputs, net and z are 16-byte aligned, by element otherwise: same
+ * bits).  Refusals, all before any launch, nothing written.  LGU_E_BADARG: N < 0, H < 1, W < 1, an unknown mode, flags
+ * other than 0, nseg outside 1..4, a null pointer among the mode's operands or one below its element's alignment.
+ * LGU_E_UNSUPPORTED: a seg_ch[i] that is not a positive multiple of 32, a sum other than 448, a Cout that does not fit the
+ * mode, a wpack that is not 16-byte aligned, H * W above 2^30, more than INT_MAX workgroups.  N == 0: LGU_OK without a launch.
+ * The operands travel in one parameter block passed by value. */
+#define LGU_GRUCONV_CIN 448
+#define LGU_GRUCONV_STEPS 126
+#define LGU_GRUCONV_MAX_SEGMENTS 4
+#define LGU_GRUCONV_WPACK_HALVES_128 516096
+#define LGU_GRUCONV_WPACK_HALVES_256 1032192
+#define LGU_GRUCONV_PLAIN 0  /* mode */
+#define LGU_GRUCONV_ZR 1     /* mode */
+#define LGU_GRUCONV_Q 2      /* mode */
+typedef struct {
+  const void* seg[4];                              /* seg[i]: (N,seg_ch[i],H,W) half, i < nseg */
+  const void* wpack; const void* bias;             /* bias: Cout halves */
+  const void* k0; const void* k1;                  /* ZR: kz, kr; Q: kq, unused */
+  const void* net; const void* z;                  /* ZR: net; Q: net, z */
+  void* out0; void* out1;                          /* PLAIN: out; ZR: z, rnet; Q: the new net */
+  int seg_ch[4]; int nseg;
+  int N, H, W, Cout, mode, flags;                  /* flags: 0 */
+} lgu_gruconv_args;
+int lgu_gruconv3x3_c448_h16(lgu_gruconv_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

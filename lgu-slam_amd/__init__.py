@@ -17,7 +17,7 @@ from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
 from .flow import FlowEncoder  # noqa: F401
 from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
-from .gru import KanBiasGRU  # noqa: F401
+from .gru import KanBiasGRU, gru_conv3x3, gru_conv_q, gru_conv_zr, pack_gruconv  # noqa: F401
 
 __version__ = "0.8.0"
 

@@ -25,6 +25,13 @@ class Conv3Args(ctypes.Structure):
                 ("Cout", _int), ("flags", _int)]
 
 
+class GruConvArgs(ctypes.Structure):
+    """lgu_gruconv_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("seg", _vp * 4), ("wpack", _vp), ("bias", _vp), ("k0", _vp), ("k1", _vp), ("net", _vp), ("z", _vp),
+                ("out0", _vp), ("out1", _vp), ("seg_ch", _int * 4), ("nseg", _int), ("N", _int), ("H", _int), ("W", _int),
+                ("Cout", _int), ("mode", _int), ("flags", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -139,6 +146,9 @@ SIGNATURES = {
     "lgu_flow_conv7_relu_h16": [FlowConv7Args, _vp],
     # 3x3 convolution, 128 in: {x, wpack, bias, out, N, H, W, Cout, flags} by value, stream
     "lgu_conv3x3_c128_h16": [Conv3Args, _vp],
+    # the GRU's 3x3 convolutions, 448 in, with gates / blend: {seg[4], wpack, bias, k0, k1, net, z, out0, out1, seg_ch[4],
+    # nseg, N, H, W, Cout, mode, flags} by value, stream
+    "lgu_gruconv3x3_c448_h16": [GruConvArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],

@@ -21,6 +21,7 @@
 // sigmoid(v) = 1 / (1 + expf(-v)), tanh = tanhf, silu(v) = v / (1 + expf(-v)): torch's device formulas in float.
 #include <limits.h>
 
+#include "kangru_math.hpp"   // rnd<T>, kg_sigmoid
 #include "lgu_common.hpp"
 
 namespace lgu {
@@ -34,10 +35,6 @@ constexpr int KG_THREADS = 256;
 constexpr int KG_CTX_PIX = LGU_KANGRU_CTX_PIXELS;  // pixels per context workgroup
 constexpr int KG_TILE = 64;                        // pixels per LDS tile (4 MFMA column tiles)
 constexpr int KG_MT = 16;                          // edges per heads workgroup
-
-
-template <typename T> __device__ __forceinline__ float rnd(float v) { return (float)(T)v; }
-__device__ __forceinline__ float kg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // MFMA step: A = 16 rows x k-slice, B = k-slice x 16 columns; C/D: lane l holds rows 4(l>>4)+i, column l&15.
 // half (16x16x32): lane l holds A[l&15][8(l>>4)+j] and B[8(l>>4)+j][l&15], j < 8.
