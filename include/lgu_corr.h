@@ -790,6 +790,43 @@ typedef struct {
 } lgu_conv3_args;
 int lgu_conv3x3_c128_h16(lgu_conv3_args args, void* stream);
 
+/* ---- update operator: the narrow heads Conv2d(128, 1 | 2, 3, padding=1) + bias (+ sigmoid | softplus) under float16 autocast
+ * (csrc/heads.hip).  Reference droid_slam/droid_net.py: delta[2], weight[2] + Sigmoid, GraphAgg.eta + GradientClip + Softplus.
+ * x (N,128,H,W) NCHW contiguous, float32, or IEEE half with LGU_HEAD_X_HALF; out (N,Cout,H,W) NCHW contiguous, IEEE half, or
+ * float32 with LGU_HEAD_SOFTPLUS; fully written and nothing outside it; Cout 1 or 2.  Rounding points:
+ *   x_h = half(x), w_h = half(weight), b_h = half(bias)     round to nearest even (x_h in the kernel, and a half x is used
+ *                                                           as it is; the others in the pack)
+ *   p_t = sum over c of x_h[c][y+ky-1][x+kx-1] * w_h[co][c][ky][kx]      t = 3 ky + kx; exact half x half products, fp32
+ *                                                           accumulation from zero in four steps of 32 channels, zero padding
+ *   s   = b_h + p_0 + p_1 + ... + p_8                        fp32, left to right
+ *   h   = half(s)                                           ONE rounding
+ *   y   = h                                                 no activation flag: half out
+ *   y   = half(1 / (1 + exp(-h)))                           LGU_HEAD_SIGMOID: evaluated in fp32, half out
+ *   y   = h > 20 ? h : log1p(exp(h))                        LGU_HEAD_SOFTPLUS (beta 1, threshold 20): fp32, float32 out
+ * All three keep a NaN.  The order is the same whatever the tile: the bits of an image depend on that image, H and W only,
+ * not on N or on its position in the batch.  A NaN or infinite input reaches exactly its 3x3 neighbourhood.  No atomics, no
+ * workspace, no host synchronisation.
+ * wpack: LGU_HEAD_WPACK_HALVES_<Cout> halves laid out [4 channel blocks kc][NT column tiles nt][64 lanes l][8 halves j] with
+ *   NT = 1 (Cout 1) or 2 (Cout 2), the B operand of v_mfma_f32_16x16x32_f16 as each lane loads it: with the column
+ *   q = 16 nt + (l & 15), element j of lane l is w_h[q % Cout][32 kc + 8 (l >> 4) + j][t / 3][t % 3] for the tap t = q / Cout
+ *   where q < 9 Cout, and zero where q >= 9 Cout (7 of 16 columns at Cout 1, 14 of 32 at Cout 2).  16-byte aligned,
+ *   otherwise LGU_E_UNSUPPORTED.  bias: Cout halves b_h.
+ * x, bias and out are read and written by element: they are served at the alignment of their element with the same bits.
+ * N == 0, H == 0 or W == 0: LGU_OK, nothing launched.  N, H or W < 0, an unknown flag, a null operand or one below its
+ * element's alignment: LGU_E_BADARG; Cout outside {1, 2}, both activation flags, a wpack that is not 16-byte aligned or more
+ * than INT_MAX workgroups (N * ceil(W / 32) * ceil(H / 4)): LGU_E_UNSUPPORTED, nothing written.
+ * The operands travel in one parameter block passed by value. */
+#define LGU_HEAD_X_HALF 1     /* flags: x holds IEEE half */
+#define LGU_HEAD_SIGMOID 2    /* flags: act = sigmoid, half out */
+#define LGU_HEAD_SOFTPLUS 4   /* flags: act = softplus, float32 out */
+#define LGU_HEAD_WPACK_HALVES_1 2048
+#define LGU_HEAD_WPACK_HALVES_2 4096
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;   /* bias: Cout halves */
+  int N, H, W, Cout, flags;
+} lgu_head_args;
+int lgu_head3x3_c128_h16(lgu_head_args args, void* stream);
+
 /* ---- KAN-bias GRU: Conv2d(448, 128, 3, padding=1) x 3 with the gates and the blend, float16 autocast (csrc/gruconv.hip) ------
  * Reference droid_slam/modules/gru_kanBias.py: convz, convr, convq of KAN_bias_GRU(128, 320).  All tensors IEEE half.
  * Input: nseg (1..4) NCHW-contiguous tensors seg[i] (N,seg_ch[i],H,W), read as their concatenation along the channels

@@ -25,6 +25,12 @@ class Conv3Args(ctypes.Structure):
                 ("Cout", _int), ("flags", _int)]
 
 
+class HeadArgs(ctypes.Structure):
+    """lgu_head_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int),
+                ("Cout", _int), ("flags", _int)]
+
+
 class GruConvArgs(ctypes.Structure):
     """lgu_gruconv_args of include/lgu_corr.h, passed by value."""
     _fields_ = [("seg", _vp * 4), ("wpack", _vp), ("bias", _vp), ("k0", _vp), ("k1", _vp), ("net", _vp), ("z", _vp),
@@ -146,6 +152,8 @@ SIGNATURES = {
     "lgu_flow_conv7_relu_h16": [FlowConv7Args, _vp],
     # 3x3 convolution, 128 in: {x, wpack, bias, out, N, H, W, Cout, flags} by value, stream
     "lgu_conv3x3_c128_h16": [Conv3Args, _vp],
+    # the narrow 3x3 heads, 128 in, Cout 1 | 2: {x, wpack, bias, out, N, H, W, Cout, flags} by value, stream
+    "lgu_head3x3_c128_h16": [HeadArgs, _vp],
     # the GRU's 3x3 convolutions, 448 in, with gates / blend: {seg[4], wpack, bias, k0, k1, net, z, out0, out1, seg_ch[4],
     # nseg, N, H, W, Cout, mode, flags} by value, stream
     "lgu_gruconv3x3_c448_h16": [GruConvArgs, _vp],
