@@ -879,6 +879,54 @@ typedef struct {
 } lgu_gruconv_args;
 int lgu_gruconv3x3_c448_h16(lgu_gruconv_args args, void* stream);
 
+/* ---- GraphAgg's upsampling mask, Conv2d(128, 576, 1) + bias under float16 autocast, alone and fused with the convex
+ * upsampling of the disparity (csrc/upmask.hip).  Reference droid_slam/droid_net.py:50-51,67 and depth_video.py:124-128.
+ * Rounding points of both entries:
+ *   x_h = half(x), w_h = half(weight), b_h = half(bias)     round to nearest even (x_h in the kernel, and a half x is used
+ *                                                           as it is; the others in the pack)
+ *   p   = sum over c of x_h[c] * w_h[co][c]                 exact half x half products, fp32 accumulation from zero in four
+ *                                                           steps of 32 channels (kc = 0..3)
+ *   h   = half(b_h[co] + p)                                 one fp32 addition, ONE rounding to half; NaN is kept
+ * The order depends on nothing but the pixel's own 128 inputs: not on N or U, the position in the batch or the launch
+ * geometry.  Both entries run the same device function for h, so the fused entry sees the bits the plain one stores.
+ * No atomics, no workspace, no allocation, no host synchronisation; launched on `stream`.
+ *
+ * lgu_upmask1x1_c128_h16  the layer.  x (N,128,H,W) NCHW contiguous, float32, or IEEE half with LGU_UPMASK_X_HALF; out
+ *   (N,576,H,W) NCHW contiguous IEEE half, fully written and nothing outside it.  A NaN or infinite input reaches exactly
+ *   its own pixel's 576 outputs.
+ * lgu_upmask_upsample_f32  the layer, then DepthVideo.upsample, in one launch, in place: x (U,128,ht,wd) as above, disps
+ *   (N,ht,wd) float, ix (U) int64, disps_up (N,8ht,8wd) float.  For u < U with 0 <= ix[u] < N, disps_up[ix[u]] =
+ *   cvx_upsample of disps[ix[u]] with the mask h of x[u], by exactly the per-output rule of lgu_cvx_upsample_f32 above on
+ *   a half mask: channel k*64 + a*8 + b weighs the neighbour (y+ky-1, x+kx-1) for the output pixel (8y+a, 8x+b); m = max_k
+ *   h_k; e_k = expf(h_k - m); s = sum e_k (ascending k); w_k = e_k / s; with LGU_UPS_HALF_WEIGHTS w_k is rounded to half
+ *   and back; out = sum w_k * d_k, each product rounded to fp32, added in ascending k; d_k = 0 outside the frame.  Only
+ *   those rows of disps_up are written; an ix[u] outside [0, N) writes nothing; with duplicates in ix the result of those
+ *   rows is unspecified among the candidates (the reference passes unique indices).  A NaN at one pixel of x reaches exactly
+ *   that pixel's 8x8 outputs.  flags: LGU_UPMASK_X_HALF | LGU_UPS_HALF_WEIGHTS.
+ * wpack: LGU_UPMASK_WPACK_HALVES halves laid out [36 row tiles mt][4 channel blocks kc][64 lanes l][8 halves j], the A
+ *   operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is w_h[16 mt + (l & 15)][32 kc + 8 (l >> 4)
+ *   + j].  Every slot holds a weight.  16-byte aligned, otherwise LGU_E_UNSUPPORTED.  bias: 576 halves b_h.
+ * x, bias, out, disps and ix are accessed by element and served at the alignment of their element with the same bits;
+ * disps_up is stored 16 bytes at a time and must be 16-byte aligned, otherwise LGU_E_UNSUPPORTED.
+ * Sizes: a negative size or an unknown flag: LGU_E_BADARG; for the fused entry ht * wd > INT_MAX / 576: LGU_E_BADARG (the
+ * rule of the upsampling entries); an empty x (N, H, W, U, ht or wd == 0) or, fused, N == 0: LGU_OK, nothing launched; a
+ * null operand or one below its element's alignment: LGU_E_BADARG; more than INT_MAX - 16 pixels in x: LGU_E_UNSUPPORTED.
+ * Every refusal comes before any launch and writes nothing.  The operands travel in one parameter block passed by value. */
+#define LGU_UPMASK_X_HALF 1   /* flags: x holds IEEE half */
+#define LGU_UPMASK_COUT 576
+#define LGU_UPMASK_WPACK_HALVES 73728
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;   /* bias: 576 halves */
+  int N, H, W, flags;
+} lgu_upmask_args;
+typedef struct {
+  const void* x; const void* wpack; const void* bias;              /* x: (U,128,ht,wd) */
+  const float* disps; const long long* ix; float* disps_up;
+  int U, N, ht, wd, flags;
+} lgu_upmask_ups_args;
+int lgu_upmask1x1_c128_h16(lgu_upmask_args args, void* stream);
+int lgu_upmask_upsample_f32(lgu_upmask_ups_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,17 @@ class HeadArgs(ctypes.Structure):
                 ("Cout", _int), ("flags", _int)]
 
 
+class UpmaskArgs(ctypes.Structure):
+    """lgu_upmask_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int), ("flags", _int)]
+
+
+class UpmaskUpsArgs(ctypes.Structure):
+    """lgu_upmask_ups_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("disps", _vp), ("ix", _vp), ("disps_up", _vp), ("U", _int),
+                ("N", _int), ("ht", _int), ("wd", _int), ("flags", _int)]
+
+
 class GruConvArgs(ctypes.Structure):
     """lgu_gruconv_args of include/lgu_corr.h, passed by value."""
     _fields_ = [("seg", _vp * 4), ("wpack", _vp), ("bias", _vp), ("k0", _vp), ("k1", _vp), ("net", _vp), ("z", _vp),
@@ -157,6 +168,10 @@ SIGNATURES = {
     # the GRU's 3x3 convolutions, 448 in, with gates / blend: {seg[4], wpack, bias, k0, k1, net, z, out0, out1, seg_ch[4],
     # nseg, N, H, W, Cout, mode, flags} by value, stream
     "lgu_gruconv3x3_c448_h16": [GruConvArgs, _vp],
+    # GraphAgg's upmask 1x1, 128 -> 576: {x, wpack, bias, out, N, H, W, flags} by value, stream
+    "lgu_upmask1x1_c128_h16": [UpmaskArgs, _vp],
+    # upmask + softmax + convex upsample: {x, wpack, bias, disps, ix, disps_up, U, N, ht, wd, flags} by value, stream
+    "lgu_upmask_upsample_f32": [UpmaskUpsArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],
