@@ -927,6 +927,41 @@ typedef struct {
 int lgu_upmask1x1_c128_h16(lgu_upmask_args args, void* stream);
 int lgu_upmask_upsample_f32(lgu_upmask_ups_args args, void* stream);
 
+/* ---- update operator: Conv2d(Cin, 128, 1) + bias (+ ReLU) under float16 autocast, 1 <= Cin <= 224 (csrc/conv1.hip).
+ * Reference droid_slam/droid_net.py: corr_encoder[0] = Conv2d(196, 128, 1) + ReLU, the consumer of the correlation lookup.
+ * x (N,Cin,H,W) NCHW contiguous, float32, or IEEE half with LGU_CONV1_X_HALF; out (N,128,H,W) NCHW contiguous IEEE half,
+ * fully written and nothing outside it.  Rounding points:
+ *   x_h = half(x), w_h = half(weight), b_h = half(bias)     round to nearest even (x_h in the kernel, and a half x is used
+ *                                                           as it is; the others in the pack)
+ *   p   = sum over c < Cin of x_h[c] * w_h[co][c]           exact half x half products, fp32 accumulation from zero in seven
+ *                                                           steps of 32 channels (kc = 0..6, ascending; channels >= Cin
+ *                                                           contribute exact zeros)
+ *   h   = half(b_h[co] + p)                                 one fp32 addition, ONE rounding to half
+ *   y   = h, or with LGU_CONV1_RELU: h < 0 ? 0 : h          a compare and select: NaN is kept
+ * The bits of a pixel depend on that pixel's Cin inputs only: not on N, the position in the batch, the pixel's group or the
+ * launch geometry.  A NaN or infinite input reaches exactly its own pixel's 128 outputs.  A channel >= Cin is never read:
+ * its staged value is written as zero.  No atomics, no workspace, no allocation, no host synchronisation.
+ * wpack: LGU_CONV1_WPACK_HALVES halves laid out [7 channel blocks kc][8 channel tiles ct][64 lanes l][8 halves j], the B
+ *   operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is w_h[16 ct + (l & 15)][c] with
+ *   c = 32 kc + 8 (l >> 4) + j where c < Cin, and zero where c >= Cin.  16-byte aligned, otherwise LGU_E_UNSUPPORTED.
+ *   bias: 128 halves b_h.
+ * x, bias and out are served at the alignment of their element with the same bits (out is stored 8 bytes at a time when
+ * H * W % 4 == 0 and it is 8-byte aligned, by element otherwise).
+ * N, H or W < 0 or an unknown flag: LGU_E_BADARG; N, H or W == 0: LGU_OK, nothing launched; a null operand or one below
+ * its element's alignment: LGU_E_BADARG; Cin outside 1..LGU_CONV1_MAX_CIN, a wpack that is not 16-byte aligned or more than
+ * INT_MAX - 32 pixels: LGU_E_UNSUPPORTED.  Every refusal comes before any launch and writes nothing.  The operands travel
+ * in one parameter block passed by value. */
+#define LGU_CONV1_COUT 128
+#define LGU_CONV1_MAX_CIN 224
+#define LGU_CONV1_WPACK_HALVES 28672
+#define LGU_CONV1_X_HALF 1   /* flags: x holds IEEE half */
+#define LGU_CONV1_RELU 2     /* flags: act = relu */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;   /* bias: 128 halves */
+  int N, Cin, H, W, flags;
+} lgu_conv1_args;
+int lgu_conv1x1_o128_h16(lgu_conv1_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, conv3, encoder, features, flow, geom, graph, gru, heads, lie, ops, sharded, upmask  # noqa: F401
+from . import _build, _lib, aggregate, ba, conv1, conv3, encoder, features, flow, geom, graph, gru, heads, lie, ops, sharded, upmask  # noqa: F401
+from . import update  # noqa: F401
+from .conv1 import Conv1  # noqa: F401
 from .conv3 import Conv3, Conv3Stack  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
@@ -20,6 +22,7 @@ from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
 from .gru import KanBiasGRU, gru_conv3x3, gru_conv_q, gru_conv_zr, pack_gruconv  # noqa: F401
 from .heads import Head  # noqa: F401
 from .upmask import Upmask  # noqa: F401
+from .update import UpdateOperator  # noqa: F401
 
 __version__ = "0.8.0"
 

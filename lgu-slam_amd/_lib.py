@@ -42,6 +42,12 @@ class UpmaskUpsArgs(ctypes.Structure):
                 ("N", _int), ("ht", _int), ("wd", _int), ("flags", _int)]
 
 
+class Conv1Args(ctypes.Structure):
+    """lgu_conv1_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("Cin", _int), ("H", _int), ("W", _int),
+                ("flags", _int)]
+
+
 class GruConvArgs(ctypes.Structure):
     """lgu_gruconv_args of include/lgu_corr.h, passed by value."""
     _fields_ = [("seg", _vp * 4), ("wpack", _vp), ("bias", _vp), ("k0", _vp), ("k1", _vp), ("net", _vp), ("z", _vp),
@@ -172,6 +178,8 @@ SIGNATURES = {
     "lgu_upmask1x1_c128_h16": [UpmaskArgs, _vp],
     # upmask + softmax + convex upsample: {x, wpack, bias, disps, ix, disps_up, U, N, ht, wd, flags} by value, stream
     "lgu_upmask_upsample_f32": [UpmaskUpsArgs, _vp],
+    # 1x1 convolution, Cin <= 224 -> 128 (corr_encoder[0]): {x, wpack, bias, out, N, Cin, H, W, flags} by value, stream
+    "lgu_conv1x1_o128_h16": [Conv1Args, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],

@@ -1,0 +1,162 @@
+"""The update operator's 1x1 convolution behind the correlation lookup (reference droid_slam/droid_net.py):
+
+    corr_encoder[0] = Conv2d(196, 128, 1), followed by ReLU
+
+Under float16 autocast, on the planar fp32 tensor the default lookup writes, the layer is a cast pass over the 784-byte
+pixel rows, the library's convolution with its layout passes, a bias launch and a ReLU launch.  `conv1x1`
+(csrc/conv1.hip) evaluates cast + convolution + bias (+ ReLU) in one launch on the matrix cores, NCHW in and NCHW out,
+with the autocast rounding points (include/lgu_corr.h), for any Conv2d(Cin, 128, 1) with 1 <= Cin <= 224.
+
+    conv1.install(update_module.corr_encoder[0])   # the Conv2d: the Sequential's ReLU stays a launch
+    y = conv1.conv1x1(corr, *wrapper.packed(), relu=True)       # the layer with its ReLU, one launch
+
+`conv1x1`: contiguous HIP device tensors only (no CPU fallback), every argument error raised before anything is launched,
+no host synchronisation (graph-capturable), forward only: an input that requires grad is refused while grad mode is on.
+There is no fp32 kernel: fp32 evaluation is the module's own forward.
+"""
+import torch
+
+from . import _lib
+from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
+                    is_conv, launch, param_key, unbind)
+from ._host import stream as _stream
+
+COUT = 128                    # include/lgu_corr.h LGU_CONV1_COUT
+MAX_CIN = 224                 # include/lgu_corr.h LGU_CONV1_MAX_CIN
+WPACK_HALVES = 28672          # include/lgu_corr.h LGU_CONV1_WPACK_HALVES = 7 * 8 * 64 * 8
+X_HALF, RELU = 1, 2           # include/lgu_corr.h LGU_CONV1_X_HALF, LGU_CONV1_RELU
+
+# The number of pixels N * H * W below which the measured fused layer does not beat the module's own autocast forward
+# beyond the two spreads (tools/prof_update.py): Conv1 sends such calls to the module.
+# 0: every measured shape class kept the fused path.
+MIN_FUSED_PIXELS = 0
+
+
+def pack_conv1(weight, bias):
+    """(wpack (7,8,64,8) half, bias_h (128) half) of a Conv2d(Cin, 128, 1) weight (128,Cin,1,1) and bias (128), 1 <= Cin <=
+    224, on the weight's device.  With c = 32 kc + 8 (l >> 4) + j: wpack[kc, ct, l, j] = half(weight)[16 ct + (l & 15), c, 0, 0]
+    where c < Cin and zero where c >= Cin: the B operand of v_mfma_f32_16x16x32_f16, one block kc of 32 input channels per
+    K step."""
+    cin = weight.shape[1] if weight.dim() == 4 and 1 <= weight.shape[1] <= MAX_CIN else MAX_CIN
+    check_shape([(weight, "weight")], (COUT, cin, 1, 1))
+    check_shape([(bias, "bias")], (COUT,))
+    with torch.no_grad():
+        wh = torch.zeros((COUT, MAX_CIN), dtype=torch.float16, device=weight.device)
+        wh[:, :cin] = weight.detach().to(torch.float16).reshape(COUT, cin)
+        # [ct][cl][kc][g][j] -> [kc][ct][g][cl][j]: lane l = 16 g + cl
+        wpack = wh.reshape(COUT // 16, 16, MAX_CIN // 32, 4, 8).permute(2, 0, 3, 1, 4).reshape(MAX_CIN // 32, COUT // 16, 64, 8)
+        wpack = wpack.contiguous()
+        bias_h = bias.detach().to(device=wh.device, dtype=torch.float16).contiguous()
+    return wpack, bias_h
+
+
+def conv1x1(x, wpack, bias_h, cin=None, relu=False):
+    """act(half(conv2d(half(x), w_h, b_h))) as a new (N,128,H,W) half tensor: x (N,Cin,H,W) float32 or half (a half x is used
+    as it is), wpack and bias_h from `pack_conv1`, act = relu if `relu` else the identity.  `cin` is the layer's number of
+    input channels, which x must have (None: x.shape[1]; the pack's slots for channels >= cin hold zero whatever it was
+    made of).  Exact products, fp32 accumulation in a fixed order, one rounding to half; NaN is kept.  x and bias_h are
+    served at element alignment; a wpack that is not 16-byte aligned (never the case for what pack_conv1 returns) raises
+    UnsupportedShape."""
+    if x.dim() != 4:
+        raise RuntimeError("x must be (N,Cin,H,W), got %s" % (tuple(x.shape),))
+    cin = x.shape[1] if cin is None else int(cin)
+    if not 1 <= cin <= MAX_CIN:
+        raise RuntimeError("conv1x1: Cin must be in 1..%d, got %d" % (MAX_CIN, cin))
+    if x.shape[1] != cin:
+        raise RuntimeError("x must be (N,%d,H,W), got %s" % (cin, tuple(x.shape)))
+    if wpack.numel() != WPACK_HALVES:
+        raise RuntimeError("wpack must hold %d halves (pack_conv1), got %s" % (WPACK_HALVES, tuple(wpack.shape)))
+    named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
+    check_shape(named[2:], (COUT,))
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:], torch.float16)
+    check_no_grad("conv1x1", named)
+    check_device(named)
+    N, _, H, W = x.shape
+    out = torch.empty((N, COUT, H, W), dtype=torch.float16, device=x.device)
+    if N == 0:
+        return out
+    if H * W == 0:
+        raise RuntimeError("conv1x1: empty frame (H*W = 0)")
+    flags = (X_HALF if x.dtype == torch.float16 else 0) | (RELU if relu else 0)
+    args = _lib.Conv1Args(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), N, cin, H, W, flags)
+    launch("lgu_conv1x1_o128_h16", "conv1x1", x.device, args, _stream(x))
+    return out
+
+
+def eligible(m):
+    """m is Conv2d(1..224, 128, 1) with a bias, stride 1, no padding, dilation, groups or padding mode."""
+    return isinstance(m, torch.nn.Conv2d) and 1 <= m.in_channels <= MAX_CIN and is_conv(m, m.in_channels, COUT, 1, pad=0, bias=True)
+
+
+def _serves(conv, x):
+    """The fused path applies to this call of an eligible `conv` on x."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != conv.in_channels:
+        return False
+    if x.dtype not in FLOAT_OR_HALF or x.shape[2] * x.shape[3] == 0:
+        return False
+    params = [conv.weight, conv.bias]
+    if any(p.dtype != torch.float32 or p.device != x.device for p in params):
+        return False
+    if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
+        return False
+    return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS
+
+
+class Conv1:
+    """Callable stand-in for the forward of one Conv2d(1..224, 128, 1) with a bias:
+
+        fused = Conv1(update_module.corr_encoder[0])
+        y = fused(corr)                        # = update_module.corr_encoder[0](corr); relu=True: = relu(conv(corr))
+
+    Fused path (csrc/conv1.hip, one launch) for a HIP tensor (N,Cin,H,W), float32 or half, under CUDA autocast with
+    float16, with float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS.
+    Everything else goes to the module's own forward unchanged (followed by relu if relu=True): CPU tensors, other
+    dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's weight and bias
+    (data pointer, version, device).  `fused_calls` counts the fused launches."""
+
+    def __init__(self, conv, relu=False):
+        if not eligible(conv):
+            raise RuntimeError("Conv1: the module must be Conv2d(1..%d, 128, 1) with a bias" % MAX_CIN)
+        self.module = conv
+        self.relu = bool(relu)
+        self._pack = None
+        self.fused_calls = 0
+
+    def packed(self):
+        """(wpack, bias_h), cached."""
+        key = param_key((self.module.weight, self.module.bias))
+        if self._pack is None or self._pack[0] != key:
+            self._pack = (key, pack_conv1(self.module.weight, self.module.bias))
+        return self._pack[1]
+
+    def __call__(self, x):
+        m = self.module
+        if not _serves(m, x):
+            y = type(m).forward(m, x)
+            return torch.relu(y) if self.relu else y
+        wpack, bias_h = self.packed()
+        y = conv1x1(x.contiguous(), wpack, bias_h, cin=m.in_channels, relu=self.relu)
+        self.fused_calls += 1
+        return y
+
+
+def install(conv, relu=False):
+    """Bind a Conv1 (`relu` as in Conv1) as `conv.forward`, an instance attribute: parameters and state_dict keys are
+    unchanged.  Returns the wrapper; a second call returns the first wrapper.  A module Conv1 does not take raises
+    RuntimeError and binds nothing, and so does a module whose forward already carries another wrapper.
+
+    `install` goes on the Conv2d, corr_encoder[0]: a conv3.Conv3Stack on corr_encoder then reaches it "as itself", in
+    either install order, and the Sequential's ReLU stays a launch of its own (update.UpdateOperator fuses it)."""
+    cur = conv.__dict__.get("forward") if isinstance(conv, torch.nn.Module) else None
+    if isinstance(cur, Conv1):
+        return cur
+    if cur is not None:
+        raise RuntimeError("conv1.install: forward already carries a %s" % type(cur).__name__)
+    return bind(conv, "forward", Conv1, lambda _: Conv1(conv, relu=relu))
+
+
+def uninstall(conv):
+    """Undo `install`: the class's forward is used again."""
+    unbind(conv, "forward", Conv1)
