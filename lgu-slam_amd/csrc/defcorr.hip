@@ -580,7 +580,9 @@ __global__ __launch_bounds__((TPX / GP) * kWave, GP == 4 ? (PROBE ? 4 : 5) : 8) 
     // clamp so that every lane forms a legal address; results of clamped lanes are discarded
     // in phase B (the loaded registers are NOT touched here, so nothing waits in phase A)
     const int xc = clampi(x1, 0, W2 - 1), yc = clampi(y1, 0, H2 - 1);
-    const bool xin = x1 + 1 < W2, yin = y1 + 1 < H2;
+    // not `x1 + 1 < W2`: at x1 = INT_MAX (a saturated conversion) the signed add wraps, the test passes and the lane,
+    // clamped to the last column, would load the element behind it — past the slice in its last row
+    const bool xin = x1 < W2 - 1, yin = y1 < H2 - 1;
     gflag[k][l] = (valid ? 1 : 0) | (xin ? 2 : 0) | (yin ? 4 : 0);
     const int dxo = xin ? step_x<TILED>(xc) : 0, dyo = yin ? step_y<TILED>(yc, W2, p.tpr[l]) : 0;
     if constexpr (PAIR) {
@@ -768,7 +770,10 @@ __global__ __launch_bounds__((TPX / GP) * kWave, GP == 4 ? (PROBE ? 4 : 5) : 8) 
     if (pxo < p.W1) {
       f16x4 o;
 #pragma unroll
-      for (int t = 0; t < 4; t++) o[t] = (_Float16)fmaxf(acc[t] + (float)bias[t], 0.0f);
+      for (int t = 0; t < 4; t++) {   // relu as torch computes it: NaN (a lookup at a NaN coordinate) stays NaN, fmaxf would return 0
+        const float v = acc[t] + (float)bias[t];
+        o[t] = (_Float16)(v < 0.0f ? 0.0f : v);
+      }
       *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(p.out) + (row_pix + pxo) * ENC_N + mt * 16 + kg * 4) = o;
     }
     return;

@@ -203,7 +203,9 @@ __global__ __launch_bounds__(NWV* kWave, 6) void defcorr_lean_kernel(
     qb[k][l] = ldg<f32x2u>(sl, pb);
     qc[k][l] = qd[k][l] = 0.0f;
     if constexpr (TILED) {
-      if (shift && x1 + 1 < W2) {  // first column of the next tile: 26 floats after the pair
+      // first column of the next tile: 26 floats after the pair.  Not `x1 + 1 < W2`: at x1 = INT_MAX (a saturated
+      // conversion) the add wraps and the clamped lane would read behind the last tile of its row, past the slice
+      if (shift && x1 < W2 - 1) {
         qc[k][l] = ldg<float>(sl, pa + 104u);
         qd[k][l] = ldg<float>(sl, pb + 104u);
       }

@@ -15,6 +15,12 @@ constexpr int kWave = 64;  // CDNA wavefront width; every kernel here is written
 __device__ __forceinline__ bool in_bounds(int h, int w, int H, int W) {
   return h >= 0 && h < H && w >= 0 && w < W;
 }
+// Range tests of an index and of its right / lower neighbour that never form `v + 1` in signed arithmetic.  A coordinate
+// beyond the int range converts to INT_MAX, and `in_bounds(h, w + 1, ..)` is then undefined: hipcc compiled its lower
+// bound as `w > -2` and its upper bound with a wrapped add, so the test PASSED at w = INT_MAX and the corner was loaded
+// from 2^31 positions past the map.  In unsigned arithmetic INT_MAX + 1 is 2^31, above every map size.
+__device__ __forceinline__ bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
+__device__ __forceinline__ bool next_in_range(int v, int n) { return (unsigned)v + 1u < (unsigned)n; }
 
 // Bilinear blend in the reference's evaluation order (defCorrSample_kernel.cu:83-86):
 // the four weights are formed in fp32 first, then Q11*w11 + Q21*w21 + Q12*w12 + Q22*w22

@@ -88,12 +88,15 @@ __global__ __launch_bounds__(LM_WAVES * kWave) void lowmem_kernel(const float* _
           const float fxs = floorf(xs), fys = floorf(ys);
           const float dx = xs - fxs, dy = ys - fys;  // :87-88
           const int h2 = (int)fys - r + iy, w2 = (int)fxs - r + ix;
-          const bool b11 = in_bounds(h2, w2, H2, W2), b21 = in_bounds(h2, w2 + 1, H2, W2);
-          const bool b12 = in_bounds(h2 + 1, w2, H2, W2), b22 = in_bounds(h2 + 1, w2 + 1, H2, W2);
+          const bool bx0 = in_range(w2, W2), bx1 = next_in_range(w2, W2), by0 = in_range(h2, H2), by1 = next_in_range(h2, H2);
+          const bool b11 = by0 && bx0, b21 = by0 && bx1, b12 = by1 && bx0, b22 = by1 && bx1;
           const float w11 = (1.0f - dy) * (1.0f - dx), w21 = (1.0f - dy) * dx;
           const float w12 = dy * (1.0f - dx), w22 = dy * dx;
-          float acc = 0.0f;
+          // no corner in the map: the reference still blends its four padded zeros (:114-117) — 0 for finite weights, NaN
+          // for the NaN weights of a NaN or infinite position
+          float acc = 0.0f * w11 + 0.0f * w21 + 0.0f * w12 + 0.0f * w22;
           if (b11 || b21 || b12 || b22) {  // wave-uniform
+            acc = 0.0f;
             const float* p11 = F2 + ((size_t)h2 * W2 + w2) * C;
 #pragma unroll
             for (int q = 0; q < Q; q++) {
@@ -245,8 +248,12 @@ __global__ __launch_bounds__(LM_WAVES * kWave) void altcorr_bwd_kernel(const flo
     for (int li = 0; li < nl; li++) {
       const int iy = li / rl, ix = li - iy * rl;
       const int h2 = (int)fys - r + iy, w2 = (int)fxs - r + ix;
-      if (!in_bounds(h2, w2, H2, W2)) continue;  // f2 = 0 and no scatter (:229-232,262-267)
       const float g = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, gl), li));
+      if (!in_bounds(h2, w2, H2, W2)) {  // f2 = 0 and no scatter (:224-227,262-267); fmap1_grad still receives g * 0 (:255),
+#pragma unroll                           // which is NaN for the NaN g of a NaN or infinite coordinate
+        for (int q = 0; q < Q; q++) f1g[q] += g * 0.0f;
+        continue;
+      }
       const float* p2 = F2 + ((size_t)h2 * W2 + w2) * C;
       float* p2g = F2G + ((size_t)h2 * W2 + w2) * C;
 #pragma unroll

@@ -478,8 +478,11 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
           for (int i = 0; i < TI; i++) res[q][i] = q11[i] * zw11 + q21[i] * zw21 + q12[i] * zw12 + q22[i] * zw22;
           if (odd) {
             asm volatile("");  // a real (scalar) branch
+            // no patch = every corner outside the map: the reference blends four padded zeros (:114-117), which is 0 for
+            // finite weights and NaN for the NaN weights of an infinite coordinate (inf - floor(inf), :87-88)
+            const float zpad = 0.f * zw11 + 0.f * zw21 + 0.f * zw12 + 0.f * zw22;
 #pragma unroll
-            for (int i = 0; i < TI; i++) res[q][i] = has_patch ? res[q][i] : 0.f;
+            for (int i = 0; i < TI; i++) res[q][i] = has_patch ? res[q][i] : zpad;
           }
         } else {
           float dxs[TI], dys[TI];
@@ -503,8 +506,8 @@ __global__ __launch_bounds__(kWave* CO_NW, CO_WPS) void lowmem_coop_kernel(const
                   t = t < NT ? t : NT - 1;
                   const int ix = t / RD;
                   const int w2 = (int)floorf(cx + o0[q][i].x) - R + ix, h2 = (int)floorf(cy + o0[q][i].y) - R + (t - ix * RD);
-                  const bool bx0 = (unsigned)w2 < (unsigned)W2, bx1 = (unsigned)(w2 + 1) < (unsigned)W2;
-                  const bool by0 = (unsigned)h2 < (unsigned)H2, by1 = (unsigned)(h2 + 1) < (unsigned)H2;
+                  const bool bx0 = in_range(w2, W2), bx1 = next_in_range(w2, W2);
+                  const bool by0 = in_range(h2, H2), by1 = next_in_range(h2, H2);
                   const float4 qq = co_corner_dots(F1 + ((size_t)h1 * W1 + w1r) * C, F2, (ptrdiff_t)h2 * W2 + w2, C, W2,
                                                    (by0 && bx0 ? 1 : 0) | (by0 && bx1 ? 2 : 0) | (by1 && bx0 ? 4 : 0) | (by1 && bx1 ? 8 : 0),
                                                    p.f2_chunked ? EPL : C, p.f2_chunked ? (ptrdiff_t)H2 * W2 * EPL : EPL);

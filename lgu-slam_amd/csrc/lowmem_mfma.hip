@@ -244,16 +244,16 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
         // taps i, j = -R..R at floor(c) + (i, j), corners one further: the lattice [f - R, f + R + 1]^2 clipped to the map
         // (= what the per-tap reduction below yields for zero offsets; the x and y ranges clip independently)
         const int fx = (int)floorf(cvv[m][q].x), fy = (int)floorf(cvv[m][q].y);
-        const int xa = fx - R > 0 ? fx - R : 0, xb = fx + R + 1 < W2 ? fx + R + 1 : W2 - 1;
-        const int ya = fy - R > 0 ? fy - R : 0, yb = fy + R + 1 < H2 ? fy + R + 1 : H2 - 1;
+        const int xa = fx > R ? fx - R : 0, xb = fx < W2 - R - 1 ? fx + R + 1 : W2 - 1;   // no signed add that can overflow
+        const int ya = fy > R ? fy - R : 0, yb = fy < H2 - R - 1 ? fy + R + 1 : H2 - 1;
         if (pv && xa <= xb && ya <= yb) { lo = pk16(xa, ya); hi = pk16(xb, yb); }
       } else {
 #pragma unroll
         for (int i = 0; i < TI; i++) {
           const float xs = cvv[m][q].x + o0[m][q][i].x, ys = cvv[m][q].y + o0[m][q][i].y;  // :82-83
           const int w2 = (int)floorf(xs) - R + tix[i], h2 = (int)floorf(ys) - R + tiy[i];
-          const int xa = w2 > 0 ? w2 : 0, xb = w2 + 1 < W2 ? w2 + 1 : W2 - 1;
-          const int ya = h2 > 0 ? h2 : 0, yb = h2 + 1 < H2 ? h2 + 1 : H2 - 1;
+          const int xa = w2 > 0 ? w2 : 0, xb = w2 < W2 - 1 ? w2 + 1 : W2 - 1;
+          const int ya = h2 > 0 ? h2 : 0, yb = h2 < H2 - 1 ? h2 + 1 : H2 - 1;
           const bool part = pv && lx + 16 * i < NT && xa <= xb && ya <= yb;  // at least one corner in bounds
           lo = part ? pk_min(lo, pk16(xa, ya)) : lo;
           hi = part ? pk_max(hi, pk16(xb, yb)) : hi;
@@ -417,8 +417,8 @@ __global__ __launch_bounds__(kWave, ZO ? 4 : (MT == 1 ? 2 : 1)) void lowmem_mfma
         }
         const int w2 = (int)fxs - R + tix[i], h2 = (int)fys - R + tiy[i];
         // per-axis range checks (one unsigned compare each), combined per corner
-        const bool bx0 = (unsigned)w2 < (unsigned)W2, bx1 = (unsigned)(w2 + 1) < (unsigned)W2;
-        const bool by0 = (unsigned)h2 < (unsigned)H2, by1 = (unsigned)(h2 + 1) < (unsigned)H2;
+        const bool bx0 = in_range(w2, W2), bx1 = next_in_range(w2, W2);
+        const bool by0 = in_range(h2, H2), by1 = next_in_range(h2, H2);
         const bool b11 = by0 && bx0, b21 = by0 && bx1, b12 = by1 && bx0, b22 = by1 && bx1;
         float q11 = 0.f, q21 = 0.f, q12 = 0.f, q22 = 0.f;
         if (tv && has_patch) {

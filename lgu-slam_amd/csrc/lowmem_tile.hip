@@ -132,8 +132,8 @@ __global__ __launch_bounds__(LT_WAVES * kWave) void lowmem_tile_kernel(const T* 
     {
       const float xs = c0v[k].x + o0[k].x, ys = c0v[k].y + o0[k].y;  // :82-83
       const int w2 = (int)floorf(xs) - R + ix, h2 = (int)floorf(ys) - R + iy;
-      const int xa = w2 > 0 ? w2 : 0, xb = w2 + 1 < W2 ? w2 + 1 : W2 - 1;
-      const int ya = h2 > 0 ? h2 : 0, yb = h2 + 1 < H2 ? h2 + 1 : H2 - 1;
+      const int xa = w2 > 0 ? w2 : 0, xb = w2 < W2 - 1 ? w2 + 1 : W2 - 1;
+      const int ya = h2 > 0 ? h2 : 0, yb = h2 < H2 - 1 ? h2 + 1 : H2 - 1;
       const bool part = pv && tap && xa <= xb && ya <= yb;  // at least one corner in bounds
       lo = part ? pk16(xa, ya) : lo;
       hi = part ? pk16(xb, yb) : hi;
@@ -290,8 +290,8 @@ __global__ __launch_bounds__(LT_WAVES * kWave) void lowmem_tile_kernel(const T* 
     const float fxs = floorf(xs), fys = floorf(ys);
     const float dx = xs - fxs, dy = ys - fys;  // :87-88
     const int w2 = (int)fxs - R + ix, h2 = (int)fys - R + iy;
-    const bool b11 = in_bounds(h2, w2, H2, W2), b21 = in_bounds(h2, w2 + 1, H2, W2);
-    const bool b12 = in_bounds(h2 + 1, w2, H2, W2), b22 = in_bounds(h2 + 1, w2 + 1, H2, W2);
+    const bool bx0 = in_range(w2, W2), bx1 = next_in_range(w2, W2), by0 = in_range(h2, H2), by1 = next_in_range(h2, H2);
+    const bool b11 = by0 && bx0, b21 = by0 && bx1, b12 = by1 && bx0, b22 = by1 && bx1;
     float q11 = 0.f, q21 = 0.f, q12 = 0.f, q22 = 0.f;
     if (tiled && bw <= LT_BOXW && bh <= LT_BOXW) {
       __builtin_amdgcn_wave_barrier();

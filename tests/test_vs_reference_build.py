@@ -287,3 +287,92 @@ def test_non_finite_coordinates_new_paths_match_reference(lgu, ref):
     b, = lgu.ops.lowMem_defSample_mixed(f1h, f2h, dev(cc), dev(fc["offset"]), 3)
     assert torch.equal(torch.isnan(a), torch.isnan(b))
     assert torch.allclose(a, b, rtol=0, atol=1e-5, equal_nan=True)
+
+
+def _same(a, b, tol, ctx):
+    a, b = a.detach().cpu().numpy().astype(np.float64), np.asarray(b, np.float64).reshape(a.shape)
+    assert np.array_equal(np.isnan(a), np.isnan(b)), "%s: NaN positions differ at %d places" % (ctx, int((np.isnan(a) != np.isnan(b)).sum()))
+    fin = ~np.isnan(a)
+    err = float(np.abs(a - b)[fin].max())
+    print("WILD reference vs restatement %s: max |err| %.3g, %d NaN" % (ctx, err, int((~fin).sum())))
+    assert err <= tol, (ctx, err)
+
+
+def test_sampler_restatement_against_the_reference_kernels_on_the_coordinate_ladder(ref, refalt):
+    """tests/sampler_restatement.py models what the device does where C says nothing: NaN -> 0 and saturation in the float ->
+    int conversion, wrapping index adds, IEEE products of padded zeros.  Here the reference's OWN kernels run its call
+    sequence (4 x defCorr_index_forward + cat, corr_index_forward, 4 x lowMem_defSample, altcorr_forward, gaussianMask) over
+    the full ladder of tests/wild_coords.py and the restatement is held to them: NaN positions exactly, values to 1e-6
+    (volume samplers) / 1e-5.  That pins the model tests/test_wild_coords.py holds every kernel of this project to.
+
+    The pin is to the reference AS COMPILED under oracle/_ref by the toolchain of this build: at a saturated coordinate its
+    own `w2 + 1` and `floor - r + i` are signed overflows, undefined in C++, which this compiler turns into wrapping adds
+    followed by `within_bounds` (the outputs below show it: zeros or NaN, never a value from the map).  The +-inf rows, which
+    saturate in the same way, are the ones this test exists for: they decide that the low-memory sampler and altcorr return
+    NaN, not 0, for an infinite coordinate.  Where the conversion is defined, the C oracle (tests/test_wild_coords.py) pins
+    the restatement without the device."""
+    from tests import sampler_restatement as S
+    from tests import wild_coords as W
+    for R in (1, 2, 3):
+        case = W.volume_case(R)
+        outs, mine = [], []
+        for l in range(4):
+            cl = (dev(case["coords"]) / 2 ** l).contiguous()
+            cn = cl.cpu().numpy()
+            od, on = dev(case["offsets"][l]), case["offsets"][l].copy()
+            a, = ref.defCorr_index_forward(dev(case["volumes"][l]), cl, od, R)
+            b, = S.defCorr_index_forward(case["volumes"][l], cn, on, R)
+            assert np.array_equal(od.cpu().numpy(), on, equal_nan=True), (R, l)
+            outs.append(a.view(3, -1, W.H1, W.W1)), mine.append(b.reshape(3, -1, W.H1, W.W1))
+            pa, = ref.corr_index_forward(dev(case["volumes"][l]), cl, R)
+            pb, = S.corr_index_forward(case["volumes"][l], cn, R)
+            _same(pa, pb, 1e-6, "corr_index_forward R=%d l=%d" % (R, l))
+        _same(torch.cat(outs, 1), np.concatenate(mine, 1), 1e-6, "4 x defCorr_index_forward + cat R=%d" % R)
+    for C in (64, 128):
+        case = W.map_case(C)
+        f1 = dev(case["fmap1"])
+        for l in range(4):
+            cl = (dev(case["coords"]) / 2 ** l).contiguous()
+            o = case["offsets"][l] if l < 2 else np.zeros_like(case["offsets"][0])
+            od, on = dev(o), o.copy()
+            a, = ref.lowMem_defSample(f1, dev(case["fmap2s"][l]), cl, od, 3)
+            b, = S.lowMem_defSample(case["fmap1"], case["fmap2s"][l], cl.cpu().numpy(), on, 3)
+            _same(a, b, 1e-5, "lowMem_defSample C=%d l=%d" % (C, l))
+            assert np.array_equal(od.cpu().numpy(), on, equal_nan=True), (C, l)
+            for r in (1, 3):
+                a, = refalt.altcorr_forward(f1, dev(case["fmap2s"][l]), cl, r)
+                b, = S.altcorr_forward(case["fmap1"], case["fmap2s"][l], cl.cpu().numpy(), r)
+                _same(a, b, 1e-5, "altcorr_forward C=%d l=%d r=%d" % (C, l, r))
+        # the backward's NaN pattern: fmap1_grad receives g * 0 from lattice points outside the map (altcorr_kernel.cu:255)
+        cl = (dev(case["coords"]) / 2).contiguous()
+        g = np.random.default_rng(90 + C).standard_normal((3, 1, 9, W.H1, W.W1)).astype(np.float32)
+        r1, r2, r3 = refalt.altcorr_backward(f1, dev(case["fmap2s"][1]), cl, dev(g), 1)
+        m1, m2, _ = S.altcorr_backward(case["fmap1"], case["fmap2s"][1], cl.cpu().numpy(), g, 1)
+        _same(r1, m1, 1e-5 * max(1.0, float(np.nanmax(np.abs(m1)))), "altcorr_backward fmap1_grad C=%d" % C)
+        _same(r2, m2, 1e-5 * max(1.0, float(np.nanmax(np.abs(m2)))), "altcorr_backward fmap2_grad C=%d" % C)
+        assert not bool(r3.any())
+    for W2 in (32, 30):
+        case = W.gauss_case(W2)
+        a, = ref.gaussianMask(dev(case["means"]), dev(case["covs"]), dev(case["volume"]), 4)
+        b, = S.gaussianMask(case["means"], case["covs"], case["volume"], 4)
+        _same(a, b, 1e-5, "gaussianMask W2=%d" % W2)
+
+
+def test_sampler_backward_on_the_coordinate_ladder_matches_reference(lgu, ref):
+    """The backward volume samplers over the whole ladder of tests/wild_coords.py (map edge, int16 and 24-bit aliases,
+    int32 rails, non-finite, wild offsets on single taps), level by level: the NaN pattern and the finite values of
+    volume_grad and offset_grad of the reference's kernels, and the same in-place state of the offsets."""
+    from tests import wild_coords as W
+    case = W.volume_case(3)
+    g = dev(np.random.default_rng(79).standard_normal((3, 7, 7, W.H1, W.W1)).astype(np.float32))
+    for l in range(4):
+        v, cl = dev(case["volumes"][l]), (dev(case["coords"]) / 2 ** l).contiguous()
+        o_r, o_m = dev(case["offsets"][l]), dev(case["offsets"][l])
+        want = ref.defCorr_index_backward(v, cl, o_r, g, 3) + ref.corr_index_backward(v, cl, g, 3)
+        got = lgu.ops.defCorr_index_backward(v, cl, o_m, g, 3) + lgu.ops.corr_index_backward(v, cl, g, 3)
+        assert np.array_equal(o_r.cpu().numpy(), o_m.cpu().numpy(), equal_nan=True), l
+        for k, (a, b) in enumerate(zip(want, got)):
+            b = b.view(a.shape)
+            assert torch.equal(torch.isnan(a), torch.isnan(b)), (l, k, int((torch.isnan(a) != torch.isnan(b)).sum()))
+            fin = ~torch.isnan(a)
+            assert bool(fin.any()) and close(b[fin], a[fin]), (l, k)
