@@ -790,6 +790,26 @@ typedef struct {
 } lgu_conv3_args;
 int lgu_conv3x3_c128_h16(lgu_conv3_args args, void* stream);
 
+/* ---- fan-out: G = 2 or 3 convolutions Conv2d(128, 128, 3, padding=1) + bias (+ ReLU) of ONE input in one launch
+ * (csrc/conv3.hip).  Reference droid_slam/droid_net.py: delta[0], weight[0] and GraphAgg.conv1 all read the GRU's result.
+ * x (N,128,H,W) as for lgu_conv3x3_c128_h16; wpack[g], bias[g], out[g] (g < G) one Cout-128 pack, its 128 bias halves and
+ * an (N,128,H,W) half output of its own, fully written and nothing outside it; entries g >= G are not read.
+ * out[g] has exactly the bits lgu_conv3x3_c128_h16 gives for x, wpack[g], bias[g] and the same flags: the tile of x is
+ * staged once, every group takes the same 36 K steps from its own bias, and no sum depends on which other channels share
+ * the launch.  A NaN of x reaches its 3x3 neighbourhood in every group, a NaN of bias[g] group g only.  No atomics, no
+ * workspace, no host synchronisation.  The outputs must not overlap x or one another.
+ * x, bias[g] and out[g] are served at the alignment of their element with the same bits: out is stored 8 bytes at a time
+ *   where W % 4 == 0 and every out[g] is 8-byte aligned, by element otherwise.
+ * N == 0: LGU_OK, nothing launched.  N < 0, H < 1, W < 1, an unknown flag, a null operand among the G groups or one below
+ * its element's alignment: LGU_E_BADARG; G outside {2, 3}, a wpack[g] that is not 16-byte aligned or more than INT_MAX
+ * workgroups (N * ceil(W / 32) * ceil(H / 4)): LGU_E_UNSUPPORTED, nothing written.  All refusals come before any launch.
+ * The operands travel in one parameter block passed by value. */
+typedef struct {
+  const void* x; const void* wpack[3]; const void* bias[3]; void* out[3];   /* bias[g]: 128 halves */
+  int N, H, W, G, flags;                                                  /* flags: LGU_CONV3_X_HALF, LGU_CONV3_RELU */
+} lgu_conv3_fanout_args;
+int lgu_conv3x3_fanout_c128_h16(lgu_conv3_fanout_args args, void* stream);
+
 /* ---- update operator: the narrow heads Conv2d(128, 1 | 2, 3, padding=1) + bias (+ sigmoid | softplus) under float16 autocast
  * (csrc/heads.hip).  Reference droid_slam/droid_net.py: delta[2], weight[2] + Sigmoid, GraphAgg.eta + GradientClip + Softplus.
  * x (N,128,H,W) NCHW contiguous, float32, or IEEE half with LGU_HEAD_X_HALF; out (N,Cout,H,W) NCHW contiguous, IEEE half, or
@@ -826,6 +846,32 @@ typedef struct {
   int N, H, W, Cout, flags;
 } lgu_head_args;
 int lgu_head3x3_c128_h16(lgu_head_args args, void* stream);
+
+/* ---- the pair of two-channel heads in one launch, edge-major (csrc/heads.hip).  Reference droid_slam/droid_net.py:
+ * delta[2] and weight[2] + Sigmoid, then view / permute / [..., :2] / contiguous; droid_slam/factor_graph.py:
+ * coords1 + float32(delta) and float32(weight) (lines 224-225 and 290-291).
+ * Head 0 reads x[0] with wpack[0], bias[0] and has no activation; head 1 reads x[1] with wpack[1], bias[1] and has the
+ * sigmoid.  x[k] (N,128,H,W) as for lgu_head3x3_c128_h16 (both float32, or both half with LGU_HEAD_X_HALF), the packs those
+ * of Cout 2.  h_k is what lgu_head3x3_c128_h16 gives for head k, bit for bit (same staging, K steps and nine-tap sum).
+ *   without LGU_HEAD_PAIR_F32   out[k] (N,H,W,2) IEEE half: out[k][n][y][x][co] = h_k[n][co][y][x]; coords must be null
+ *   with LGU_HEAD_PAIR_F32      out[k] (N,H,W,2) float32, coords (N,H,W,2) float32, not null:
+ *                               out[0] = coords + float(h_0)   one fp32 addition; coords is read at that element only
+ *                               out[1] = float(h_1)
+ * Outputs are fully written and nothing outside them; a pixel's two channels are one 4-byte (half) or 8-byte (float32)
+ * store, and coords is read 8 bytes at a time.  No atomics, no workspace, no host synchronisation.
+ * x[k] and bias[k] are served at the alignment of their element with the same bits.
+ * N == 0, H == 0 or W == 0: LGU_OK, nothing launched.  N, H or W < 0, an unknown flag, LGU_HEAD_PAIR_F32 without coords or
+ * coords without it, a null operand or one below its element's alignment: LGU_E_BADARG; a wpack[k] that is not 16-byte
+ * aligned, an out[k] or coords that is not aligned to a whole pixel (4 bytes half, 8 bytes float32) or more than INT_MAX
+ * workgroups (2 * N * ceil(W / 32) * ceil(H / 4)): LGU_E_UNSUPPORTED, nothing written.  All refusals come before any launch.
+ * The operands travel in one parameter block passed by value. */
+#define LGU_HEAD_PAIR_F32 8   /* flags of lgu_head3x3_pair_c128_h16: float32 outputs, out[0] = coords + delta */
+typedef struct {
+  const void* x[2]; const void* wpack[2]; const void* bias[2]; void* out[2];   /* bias[k]: 2 halves */
+  const void* coords;                                                          /* null without LGU_HEAD_PAIR_F32 */
+  int N, H, W, flags;
+} lgu_head_pair_args;
+int lgu_head3x3_pair_c128_h16(lgu_head_pair_args args, void* stream);
 
 /* ---- KAN-bias GRU: Conv2d(448, 128, 3, padding=1) x 3 with the gates and the blend, float16 autocast (csrc/gruconv.hip) ------
  * Reference droid_slam/modules/gru_kanBias.py: convz, convr, convq of KAN_bias_GRU(128, 320).  All tensors IEEE half.

@@ -13,14 +13,14 @@ import sys
 from . import _build, _lib, aggregate, ba, conv1, conv3, encoder, features, flow, geom, graph, gru, heads, lie, ops, sharded, upmask  # noqa: F401
 from . import update  # noqa: F401
 from .conv1 import Conv1  # noqa: F401
-from .conv3 import Conv3, Conv3Stack  # noqa: F401
+from .conv3 import Conv3, Conv3Stack, conv3x3_fanout  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
 from .flow import FlowEncoder  # noqa: F401
 from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
 from .gru import KanBiasGRU, gru_conv3x3, gru_conv_q, gru_conv_zr, pack_gruconv  # noqa: F401
-from .heads import Head  # noqa: F401
+from .heads import Head, head_pair  # noqa: F401
 from .upmask import Upmask  # noqa: F401
 from .update import UpdateOperator  # noqa: F401
 

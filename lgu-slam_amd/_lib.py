@@ -31,6 +31,18 @@ class HeadArgs(ctypes.Structure):
                 ("Cout", _int), ("flags", _int)]
 
 
+class Conv3FanoutArgs(ctypes.Structure):
+    """lgu_conv3_fanout_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp * 3), ("bias", _vp * 3), ("out", _vp * 3), ("N", _int), ("H", _int), ("W", _int),
+                ("G", _int), ("flags", _int)]
+
+
+class HeadPairArgs(ctypes.Structure):
+    """lgu_head_pair_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp * 2), ("wpack", _vp * 2), ("bias", _vp * 2), ("out", _vp * 2), ("coords", _vp), ("N", _int), ("H", _int),
+                ("W", _int), ("flags", _int)]
+
+
 class UpmaskArgs(ctypes.Structure):
     """lgu_upmask_args of include/lgu_corr.h, passed by value."""
     _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int), ("flags", _int)]
@@ -171,6 +183,10 @@ SIGNATURES = {
     "lgu_conv3x3_c128_h16": [Conv3Args, _vp],
     # the narrow 3x3 heads, 128 in, Cout 1 | 2: {x, wpack, bias, out, N, H, W, Cout, flags} by value, stream
     "lgu_head3x3_c128_h16": [HeadArgs, _vp],
+    # 2 or 3 convolutions 128 -> 128 of one input: {x, wpack[3], bias[3], out[3], N, H, W, G, flags} by value, stream
+    "lgu_conv3x3_fanout_c128_h16": [Conv3FanoutArgs, _vp],
+    # delta[2] and weight[2] in one launch, edge-major: {x[2], wpack[2], bias[2], out[2], coords, N, H, W, flags} by value, stream
+    "lgu_head3x3_pair_c128_h16": [HeadPairArgs, _vp],
     # the GRU's 3x3 convolutions, 448 in, with gates / blend: {seg[4], wpack, bias, k0, k1, net, z, out0, out1, seg_ch[4],
     # nseg, N, H, W, Cout, mode, flags} by value, stream
     "lgu_gruconv3x3_c448_h16": [GruConvArgs, _vp],

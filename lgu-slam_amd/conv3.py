@@ -32,6 +32,11 @@ X_HALF, RELU = 1, 2              # include/lgu_corr.h LGU_CONV3_X_HALF, LGU_CONV
 # forward beyond the two spreads (tools/prof_conv3.py): Conv3 and Conv3Stack send such calls to the
 # module.  0: every measured shape class kept the fused path.
 MIN_FUSED_PIXELS = {64: 0, 128: 0}
+# The number of pixels N * H * W below which `conv3x3_fanout` does not beat the separate `conv3x3` launches beyond the two
+# spreads (tools/prof_outstage.py): UpdateOperator takes the separate launches below it.
+# 80 x 60x80 keeps the fan-out (G = 3: 458 against 539 us); 48 x 48x64 does not at G = 3 (169 +- 10 against 181 +- 10 us:
+# inside the spreads), and one threshold cannot keep 1 x 48x64 (37 against 49 us) without it.
+MIN_FANOUT_PIXELS = 384000
 
 
 def pack_conv3(weight, bias):
@@ -79,6 +84,43 @@ def conv3x3(x, wpack, bias_h, relu=False):
     args = _lib.Conv3Args(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), N, H, W, cout, flags)
     launch("lgu_conv3x3_c128_h16", "conv3x3", x.device, args, _stream(x))
     return out
+
+
+def conv3x3_fanout(x, packs, relu=False):
+    """Two or three Conv2d(128, 128, 3, padding=1) of ONE input in one launch: a tuple of len(packs) new (N,128,H,W) half
+    tensors, output g with the bits of conv3x3(x, *packs[g], relu=relu).  x (N,128,H,W) float32 or half; packs a sequence of
+    two or three (wpack, bias_h) of `pack_conv3` with Cout 128.  The tile of x is staged once for all of them.  x and the
+    biases are served at element alignment; a wpack that is not 16-byte aligned raises UnsupportedShape."""
+    if x.dim() != 4 or x.shape[1] != CIN:
+        raise RuntimeError("x must be (N,%d,H,W), got %s" % (CIN, tuple(x.shape)))
+    packs = [tuple(p) for p in packs]
+    if len(packs) not in (2, 3) or any(len(p) != 2 for p in packs):
+        raise RuntimeError("packs must be two or three (wpack, bias_h) pairs (pack_conv3), got %d" % len(packs))
+    named = [(x, "x")]
+    for g, (wpack, bias_h) in enumerate(packs):
+        if wpack.numel() != WPACK_HALVES[128]:
+            raise RuntimeError("packs[%d]: wpack must hold %d halves (pack_conv3, Cout 128), got %s"
+                               % (g, WPACK_HALVES[128], tuple(wpack.shape)))
+        check_shape([(bias_h, "packs[%d]: bias_h" % g)], (128,))
+        named += [(wpack, "packs[%d]: wpack" % g), (bias_h, "packs[%d]: bias_h" % g)]
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:], torch.float16)
+    check_no_grad("conv3x3_fanout", named)
+    check_device(named)
+    N, _, H, W = x.shape
+    outs = tuple(torch.empty((N, 128, H, W), dtype=torch.float16, device=x.device) for _ in packs)
+    if N == 0:
+        return outs
+    if H * W == 0:
+        raise RuntimeError("conv3x3_fanout: empty frame (H*W = 0)")
+    G = len(packs)
+    three = _lib._vp * 3
+    flags = (X_HALF if x.dtype == torch.float16 else 0) | (RELU if relu else 0)
+    args = _lib.Conv3FanoutArgs(x.data_ptr(), three(*[p[0].data_ptr() for p in packs]), three(*[p[1].data_ptr() for p in packs]),
+                                three(*[o.data_ptr() for o in outs]), N, H, W, G, flags)
+    launch("lgu_conv3x3_fanout_c128_h16", "conv3x3_fanout", x.device, args, _stream(x))
+    return outs
 
 
 def eligible(m):

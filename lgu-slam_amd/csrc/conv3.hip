@@ -21,6 +21,10 @@
 // accumulators start at the bias.  The result goes back through LDS as [channel][pixel] so that a store instruction
 // writes 64- or 128-byte runs of a channel's row, 16 bytes per lane (or by element where out or W do not allow).
 // No atomics, no workspace, no host synchronisation.
+//
+// conv3x3_fanout_c128_kernel runs two or three such 128 -> 128 layers of ONE input (delta[0], weight[0], agg.conv1 behind
+// the GRU) in one launch: the same staging once, then the same K loop per group.  The phases are device functions shared
+// by both kernels, so an output of the fan-out has the bits of the single layer.
 #include <limits.h>
 
 #include <type_traits>
@@ -57,44 +61,25 @@ constexpr int c3_lds_bytes() {
   return (C3_MT / TXM + 2) * (16 * TXM + 2) * C3_PITCH;
 }
 
-template <int COUT, int TXM, bool XH>
-__global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __restrict__ xv, const f16x8* __restrict__ wpack,
-                                                                 const _Float16* __restrict__ bias,
-                                                                 _Float16* __restrict__ out, int H, int W, int tiles_x,
-                                                                 int tiles_y, int relu, int vec) {
-  using XT = typename std::conditional<XH, _Float16, float>::type;
-  constexpr int TX = 16 * TXM, TY = C3_MT / TXM;
-  constexpr int LW = TX + 2, LH = TY + 2;
-  constexpr int NCT = COUT / 32;           // channel tiles per wave
-  constexpr int CTS = COUT / 16;           // channel tiles in the pack
-  static_assert(COUT * C3_OPITCH <= LH * LW * C3_PITCH, "the output image reuses the input tile's LDS");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-  int b = blockIdx.x;
-  const int x0 = (b % tiles_x) * TX;
-  b /= tiles_x;
-  const int y0 = (b % tiles_y) * TY;
-  const int n = b / tiles_y;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-  const int p = lane & 15, g = lane >> 4;
-  const int wr = w >> 1, wc = w & 1;
-  const size_t HW = (size_t)H * W;
-
-  // the wave's first weight fragments and its bias are in flight while the tile is staged
-  const f16x8* wp = wpack + (size_t)(wc * NCT) * kWave + lane;
-  f16x8 bf[C3_PF][NCT];
+// ---- the three phases every kernel of this file is made of.  They are shared, not copied: an output element's bits are
+// those of c3_mma's order and nothing else.
+// the first C3_PF K steps' weight fragments of a wave (wp: the pack at the wave's first channel tile and lane)
+template <int NCT, int CTS>
+__device__ __forceinline__ void c3_prefetch(const f16x8* __restrict__ wp, f16x8 (&bf)[C3_PF][NCT]) {
 #pragma unroll
   for (int s = 0; s < C3_PF; s++)
 #pragma unroll
     for (int ct = 0; ct < NCT; ct++) bf[s][ct] = wp[((size_t)s * CTS + ct) * kWave];
-  float bz[NCT];
-#pragma unroll
-  for (int ct = 0; ct < NCT; ct++) bz[ct] = (float)bias[wc * 16 * NCT + 16 * ct + p];
+}
 
-  // stage: one (channel octet, row, pixel) per thread and item, lanes along x; the loads of C3_SU items are issued
-  // before the first of them is converted and written (a pixel outside the image re-reads the image's first pixel and
-  // is then zeroed: every load is unconditional)
-  const XT* src = static_cast<const XT*>(xv) + (size_t)n * C3_CI * HW;
+// stage: one (channel octet, row, pixel) per thread and item, lanes along x; the loads of C3_SU items are issued before
+// the first of them is converted and written (a pixel outside the image re-reads the image's first pixel and is then
+// zeroed: every load is unconditional)
+template <int TXM, typename XT>
+__device__ __forceinline__ void c3_stage(unsigned char* smem, const XT* __restrict__ src, int y0, int x0, int H, int W, size_t HW,
+                                         int tid) {
+  constexpr int TX = 16 * TXM, TY = C3_MT / TXM;
+  constexpr int LW = TX + 2, LH = TY + 2;
   constexpr int ITEMS = 16 * LH * LW;
   for (int base = tid; base < ITEMS; base += C3_SU * C3_THREADS) {
     XT raw[C3_SU][8];
@@ -123,15 +108,18 @@ __global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __
       }
     }
   }
-  __syncthreads();
+}
 
-  f32x4 acc[4][NCT];
+// the 36 K steps of a wave's 4 pixel tiles x NCT channel tiles, from the bias: tap-major (ky, kx), then channel block.
+// bf holds the fragments of steps 0 .. C3_PF - 1 on entry and is used up on return.
+template <int NCT, int CTS, int TXM>
+__device__ __forceinline__ void c3_mma(const unsigned char* abase, const f16x8* __restrict__ wp, f16x8 (&bf)[C3_PF][NCT],
+                                       const float (&bz)[NCT], int wr, f32x4 (&acc)[4][NCT]) {
+  constexpr int LW = 16 * TXM + 2;
 #pragma unroll
   for (int m = 0; m < 4; m++)
 #pragma unroll
     for (int ct = 0; ct < NCT; ct++) acc[m][ct] = f32x4{bz[ct], bz[ct], bz[ct], bz[ct]};
-
-  const unsigned char* abase = smem + p * C3_PITCH + 16 * g;
 #pragma unroll
   for (int s = 0; s < 36; s++) {
     const int tap = s >> 2, kc = s & 3, ky = tap / 3, kx = tap % 3;
@@ -154,6 +142,55 @@ __global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __
       for (int ct = 0; ct < NCT; ct++)
         acc[m][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m], bw[ct], acc[m][ct], 0, 0, 0);
   }
+}
+
+// one rounding to half, then the ReLU (a NaN compares false and is kept)
+__device__ __forceinline__ f16x4 c3_round(const f32x4& v, int relu) {
+  f16x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const _Float16 h = (_Float16)v[i];
+    o[i] = (relu && h < (_Float16)0.0f) ? (_Float16)0.0f : h;
+  }
+  return o;
+}
+
+template <int COUT, int TXM, bool XH>
+__global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __restrict__ xv, const f16x8* __restrict__ wpack,
+                                                                 const _Float16* __restrict__ bias,
+                                                                 _Float16* __restrict__ out, int H, int W, int tiles_x,
+                                                                 int tiles_y, int relu, int vec) {
+  using XT = typename std::conditional<XH, _Float16, float>::type;
+  constexpr int TX = 16 * TXM, TY = C3_MT / TXM;
+  constexpr int LW = TX + 2, LH = TY + 2;
+  constexpr int NCT = COUT / 32;           // channel tiles per wave
+  constexpr int CTS = COUT / 16;           // channel tiles in the pack
+  static_assert(COUT * C3_OPITCH <= LH * LW * C3_PITCH, "the output image reuses the input tile's LDS");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  int b = blockIdx.x;
+  const int x0 = (b % tiles_x) * TX;
+  b /= tiles_x;
+  const int y0 = (b % tiles_y) * TY;
+  const int n = b / tiles_y;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
+  const int p = lane & 15, g = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;
+  const size_t HW = (size_t)H * W;
+
+  // the wave's first weight fragments and its bias are in flight while the tile is staged
+  const f16x8* wp = wpack + (size_t)(wc * NCT) * kWave + lane;
+  f16x8 bf[C3_PF][NCT];
+  c3_prefetch<NCT, CTS>(wp, bf);
+  float bz[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ct++) bz[ct] = (float)bias[wc * 16 * NCT + 16 * ct + p];
+
+  c3_stage<TXM, XT>(smem, static_cast<const XT*>(xv) + (size_t)n * C3_CI * HW, y0, x0, H, W, HW, tid);
+  __syncthreads();
+
+  f32x4 acc[4][NCT];
+  c3_mma<NCT, CTS, TXM>(smem + p * C3_PITCH + 16 * g, wp, bf, bz, wr, acc);
   __syncthreads();   // every wave has read its last A fragment: the tile's LDS becomes the output image
 
   // [channel][pixel tile][16 pixels] half; a lane's four accumulators are four consecutive pixels of one channel
@@ -161,14 +198,8 @@ __global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __
   for (int m = 0; m < 4; m++)
 #pragma unroll
     for (int ct = 0; ct < NCT; ct++) {
-      f16x4 o;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const _Float16 h = (_Float16)acc[m][ct][i];
-        o[i] = (relu && h < (_Float16)0.0f) ? (_Float16)0.0f : h;   // a NaN compares false and is kept
-      }
       const int co = wc * 16 * NCT + 16 * ct + p, mt = 4 * wr + m;
-      *reinterpret_cast<f16x4*>(smem + co * C3_OPITCH + 2 * (16 * mt + 4 * g)) = o;
+      *reinterpret_cast<f16x4*>(smem + co * C3_OPITCH + 2 * (16 * mt + 4 * g)) = c3_round(acc[m][ct], relu);
     }
   __syncthreads();
 
@@ -187,6 +218,78 @@ __global__ __launch_bounds__(C3_THREADS) void conv3x3_c128_kernel(const void* __
 #pragma unroll
       for (int i = 0; i < 8; i++)
         if (xo + i < W) q[i] = v[i];
+    }
+  }
+}
+
+// ---- fan-out: G = 2 or 3 convolutions 128 -> 128 of ONE input.  The tile is staged once; each group then takes its own
+// 36 K steps (c3_mma, so output g has the bits of conv3x3_c128_kernel with pack g) and is stored straight from the
+// accumulators, because the tile must survive to the last group: a lane's four accumulators are four consecutive pixels
+// of one channel, one 8-byte store where W % 4 == 0 and the outputs are 8-byte aligned, by element otherwise.  The next
+// group's first weight fragments are in flight while a group is stored.
+struct C3FanOperands {
+  const f16x8* wpack[3];
+  const _Float16* bias[3];
+  _Float16* out[3];
+};
+
+template <int TXM, bool XH>
+__global__ __launch_bounds__(C3_THREADS, 2) void conv3x3_fanout_c128_kernel(const void* __restrict__ xv, C3FanOperands ops, int G,
+                                                                        int H, int W, int tiles_x, int tiles_y, int relu,
+                                                                        int vec) {
+  using XT = typename std::conditional<XH, _Float16, float>::type;
+  constexpr int COUT = 128, NCT = COUT / 32, CTS = COUT / 16;
+  constexpr int TX = 16 * TXM, TY = C3_MT / TXM;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+  int b = blockIdx.x;
+  const int x0 = (b % tiles_x) * TX;
+  b /= tiles_x;
+  const int y0 = (b % tiles_y) * TY;
+  const int n = b / tiles_y;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
+  const int p = lane & 15, g = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;
+  const size_t HW = (size_t)H * W;
+  const size_t woff = (size_t)(wc * NCT) * kWave + lane;
+
+  f16x8 bf[C3_PF][NCT];
+  c3_prefetch<NCT, CTS>(ops.wpack[0] + woff, bf);
+  c3_stage<TXM, XT>(smem, static_cast<const XT*>(xv) + (size_t)n * C3_CI * HW, y0, x0, H, W, HW, tid);
+  __syncthreads();
+
+#pragma unroll 1
+  for (int grp = 0; grp < G; grp++) {
+    // the staged tile does not change between the groups, and the compiler knows it: without this it hoists all 144 A
+    // fragments of the K loop (576 registers) out of the group loop and spills them
+    asm volatile("" ::: "memory");
+    // block-uniform selects of kernel arguments: no indexed private array
+    const f16x8* wp = (grp == 0 ? ops.wpack[0] : grp == 1 ? ops.wpack[1] : ops.wpack[2]) + woff;
+    const _Float16* bias = grp == 0 ? ops.bias[0] : grp == 1 ? ops.bias[1] : ops.bias[2];
+    _Float16* dst = (grp == 0 ? ops.out[0] : grp == 1 ? ops.out[1] : ops.out[2]) + (size_t)n * COUT * HW;
+    float bz[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++) bz[ct] = (float)bias[wc * 16 * NCT + 16 * ct + p];
+    f32x4 acc[4][NCT];
+    c3_mma<NCT, CTS, TXM>(smem + p * C3_PITCH + 16 * g, wp, bf, bz, wr, acc);
+    if (grp + 1 < G) c3_prefetch<NCT, CTS>((grp == 0 ? ops.wpack[1] : ops.wpack[2]) + woff, bf);
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      const int mt = 4 * wr + m, row = mt / TXM, mtx = mt % TXM;
+      const int y = y0 + row, xo = x0 + 16 * mtx + 4 * g;
+      if (y >= H || xo >= W) continue;
+#pragma unroll
+      for (int ct = 0; ct < NCT; ct++) {
+        const f16x4 o = c3_round(acc[m][ct], relu);
+        _Float16* q = dst + (size_t)(wc * 16 * NCT + 16 * ct + p) * HW + (size_t)y * W + xo;
+        if (vec) {
+          *reinterpret_cast<f16x4*>(q) = o;   // W % 4 == 0 and out 8-byte aligned: four pixels in or out together
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+            if (xo + i < W) q[i] = o[i];
+        }
+      }
     }
   }
 }
@@ -213,7 +316,57 @@ static int c3_launch_x(const lgu_conv3_args& a, hipStream_t s) {
   return (a.flags & LGU_CONV3_X_HALF) ? c3_launch<COUT, TXM, true>(a, s) : c3_launch<COUT, TXM, false>(a, s);
 }
 
+template <int TXM, bool XH>
+static int c3_fan_launch(const lgu_conv3_fanout_args& a, hipStream_t s) {
+  constexpr int TX = 16 * TXM, TY = C3_MT / TXM;
+  const int tiles_x = (a.W - 1) / TX + 1, tiles_y = (a.H - 1) / TY + 1;
+  const long long blocks = (long long)a.N * tiles_x * tiles_y;
+  if (blocks > INT_MAX) return LGU_E_UNSUPPORTED;
+  auto kern = conv3x3_fanout_c128_kernel<TXM, XH>;
+  if (allow_max_dynamic_lds<conv3x3_fanout_c128_kernel<TXM, XH>>() != hipSuccess) return launch_status();
+  C3FanOperands ops;
+  int vec = a.W % 4 == 0 ? 1 : 0;
+  for (int g = 0; g < 3; g++) {   // an unused third slot repeats the second: the kernel never reads it
+    const int k = g < a.G ? g : a.G - 1;
+    ops.wpack[g] = static_cast<const f16x8*>(a.wpack[k]);
+    ops.bias[g] = static_cast<const _Float16*>(a.bias[k]);
+    ops.out[g] = static_cast<_Float16*>(a.out[k]);
+    if (!c3_aligned(a.out[k], 8)) vec = 0;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C3_THREADS), c3_lds_bytes<TXM>(), s, a.x, ops, a.G, a.H, a.W, tiles_x,
+                     tiles_y, (a.flags & LGU_CONV3_RELU) ? 1 : 0, vec);
+  return launch_status();
+}
+
+template <int TXM>
+static int c3_fan_launch_x(const lgu_conv3_fanout_args& a, hipStream_t s) {
+  return (a.flags & LGU_CONV3_X_HALF) ? c3_fan_launch<TXM, true>(a, s) : c3_fan_launch<TXM, false>(a, s);
+}
+
 }  // namespace lgu
+
+extern "C" int lgu_conv3x3_fanout_c128_h16(lgu_conv3_fanout_args a, void* stream) {
+  using namespace lgu;
+  if (a.N < 0 || a.H < 1 || a.W < 1 || (a.flags & ~(LGU_CONV3_X_HALF | LGU_CONV3_RELU))) return LGU_E_BADARG;
+  if (a.N == 0) return LGU_OK;
+  if (a.G != 2 && a.G != 3) return LGU_E_UNSUPPORTED;
+  if (!a.x || !c3_aligned(a.x, (a.flags & LGU_CONV3_X_HALF) ? 2 : 4)) return LGU_E_BADARG;
+  for (int g = 0; g < a.G; g++) {
+    if (!a.wpack[g] || !a.bias[g] || !a.out[g]) return LGU_E_BADARG;
+    if (!c3_aligned(a.bias[g], 2) || !c3_aligned(a.out[g], 2)) return LGU_E_BADARG;
+  }
+  for (int g = 0; g < a.G; g++)
+    if (!c3_aligned(a.wpack[g], 16)) return LGU_E_UNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // always 32 x 4 pixels per workgroup (the bits do not depend on the tile): the 64-wide tile's whole 128-byte lines come
+  // from the write-out through LDS, which this kernel does not have, and the taller tile stages less halo; measured
+  // faster at every shape class
+#if LGU_C3_FORCE_TXM == 4
+  return c3_fan_launch_x<4>(a, s);
+#else
+  return c3_fan_launch_x<2>(a, s);
+#endif
+}
 
 extern "C" int lgu_conv3x3_c128_h16(lgu_conv3_args a, void* stream) {
   using namespace lgu;

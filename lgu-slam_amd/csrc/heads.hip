@@ -24,6 +24,9 @@
 // 16-byte store).  After the barrier thread (co, ty, tx) adds its nine partials to the bias in the order t = 0..8 (lanes
 // along tx: conflict-free) and stores one element, lanes along x.  The order never depends on the tile, the batch or N.
 // A pixel outside the image is staged as zero and its partials are +0.  No atomics, no workspace, no host synchronisation.
+//
+// head3x3_pair_c128_kernel runs delta[2] and weight[2] + Sigmoid in one launch (the head follows the block index) and
+// writes them edge-major, (N,H,W,2), one store per pixel; optionally as float32 with delta added to the coordinates.
 #include <limits.h>
 
 #include <type_traits>
@@ -58,26 +61,13 @@ __device__ __forceinline__ float hd_softplus(float v) {   // beta 1, threshold 2
   return v > 20.0f ? v : log1pf(expf(v));
 }
 
-template <int COUT, bool XH, int ACT>   // ACT 0: none, 1: sigmoid, 2: softplus (float32 out)
-__global__ __launch_bounds__(HD_THREADS) void head3x3_c128_kernel(const void* __restrict__ xv, const f16x8* __restrict__ wpack,
-                                                                 const _Float16* __restrict__ bias, void* __restrict__ outv,
-                                                                 int H, int W, int tiles_x, int tiles_y) {
-  using XT = typename std::conditional<XH, _Float16, float>::type;
-  using OT = typename std::conditional<ACT == 2, float, _Float16>::type;
-  constexpr int NP = 9 * COUT;             // columns of partials
-  constexpr int NT = (NP + 15) / 16;       // MFMA column tiles
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* part = reinterpret_cast<float*>(smem + HD_XBYTES);
-
-  int b = blockIdx.x;
-  const int x0 = (b % tiles_x) * HD_TX;
-  b /= tiles_x;
-  const int y0 = (b % tiles_y) * HD_TY;
-  const int n = b / tiles_y;
+// ---- the phases every kernel of this file shares: the wave's weight fragments, the staging of the tile, the MFMA phase
+// and the partials in LDS.  On return (behind a barrier) part holds [column][staged pixel] fp32.
+template <int NT, int NP, typename XT>
+__device__ __forceinline__ void hd_partials(unsigned char* smem, float* part, const XT* __restrict__ src,
+                                            const f16x8* __restrict__ wpack, int y0, int x0, int H, int W, size_t HW) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
   const int p = lane & 15, g = lane >> 4;
-  const size_t HW = (size_t)H * W;
-
   // the wave's weight fragments are in flight while the tile is staged
   f16x8 bw[4][NT];
 #pragma unroll
@@ -87,7 +77,6 @@ __global__ __launch_bounds__(HD_THREADS) void head3x3_c128_kernel(const void* __
 
   // stage (csrc/conv3.hip): one (channel octet, row, pixel) per thread and item, lanes along x; a pixel outside the image
   // re-reads the image's first pixel and is then zeroed, so every load is unconditional
-  const XT* src = static_cast<const XT*>(xv) + (size_t)n * HD_CI * HW;
   constexpr int ITEMS = 16 * HD_PIX;
   for (int base = tid; base < ITEMS; base += HD_SU * HD_THREADS) {
     XT raw[HD_SU][8];
@@ -144,6 +133,28 @@ __global__ __launch_bounds__(HD_THREADS) void head3x3_c128_kernel(const void* __
     }
   }
   __syncthreads();
+}
+
+template <int COUT, bool XH, int ACT>   // ACT 0: none, 1: sigmoid, 2: softplus (float32 out)
+__global__ __launch_bounds__(HD_THREADS) void head3x3_c128_kernel(const void* __restrict__ xv, const f16x8* __restrict__ wpack,
+                                                                 const _Float16* __restrict__ bias, void* __restrict__ outv,
+                                                                 int H, int W, int tiles_x, int tiles_y) {
+  using XT = typename std::conditional<XH, _Float16, float>::type;
+  using OT = typename std::conditional<ACT == 2, float, _Float16>::type;
+  constexpr int NP = 9 * COUT;             // columns of partials
+  constexpr int NT = (NP + 15) / 16;       // MFMA column tiles
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* part = reinterpret_cast<float*>(smem + HD_XBYTES);
+
+  int b = blockIdx.x;
+  const int x0 = (b % tiles_x) * HD_TX;
+  b /= tiles_x;
+  const int y0 = (b % tiles_y) * HD_TY;
+  const int n = b / tiles_y;
+  const int tid = threadIdx.x;
+  const size_t HW = (size_t)H * W;
+
+  hd_partials<NT, NP, XT>(smem, part, static_cast<const XT*>(xv) + (size_t)n * HD_CI * HW, wpack, y0, x0, H, W, HW);
 
   const int co = tid / (HD_TX * HD_TY), pix = tid % (HD_TX * HD_TY);
   const int ty = pix / HD_TX, tx = pix % HD_TX;
@@ -171,6 +182,86 @@ static int hd_launch(const lgu_head_args& a, unsigned blocks, int tiles_x, int t
   if (allow_max_dynamic_lds<head3x3_c128_kernel<COUT, XH, ACT>>() != hipSuccess) return launch_status();
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(HD_THREADS), hd_lds_bytes<COUT>(), s, a.x, static_cast<const f16x8*>(a.wpack),
                      static_cast<const _Float16*>(a.bias), a.out, a.H, a.W, tiles_x, tiles_y);
+  return launch_status();
+}
+
+// ---- the pair: delta[2] (head 0, no activation) and weight[2] (head 1, sigmoid) in one launch, edge-major.  Blocks
+// [0, tiles) are head 0 and [tiles, 2 tiles) head 1; the input, pack, bias and output follow the head.  hd_partials and
+// the nine-tap sum are head3x3_c128_kernel<2, XH, .>'s, so h has its bits.  One thread owns one pixel and stores both
+// channels together: (N,H,W,2) half, or float32 with F32, where head 0 adds h to coords at that element (one fp32 add).
+struct HdPairOperands {
+  const void* x[2];
+  const f16x8* wpack[2];
+  const _Float16* bias[2];
+  void* out[2];
+  const float* coords;
+};
+
+template <bool XH, bool F32>
+__global__ __launch_bounds__(HD_THREADS) void head3x3_pair_c128_kernel(HdPairOperands ops, int H, int W, int tiles_x, int tiles_y,
+                                                                      int tiles) {
+  using XT = typename std::conditional<XH, _Float16, float>::type;
+  constexpr int NP = 18, NT = 2;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* part = reinterpret_cast<float*>(smem + HD_XBYTES);
+
+  int b = blockIdx.x;
+  const int head = b >= tiles ? 1 : 0;     // block-uniform
+  b -= head * tiles;
+  const int x0 = (b % tiles_x) * HD_TX;
+  b /= tiles_x;
+  const int y0 = (b % tiles_y) * HD_TY;
+  const int n = b / tiles_y;
+  const int tid = threadIdx.x;
+  const size_t HW = (size_t)H * W;
+  const XT* src = static_cast<const XT*>(head ? ops.x[1] : ops.x[0]) + (size_t)n * HD_CI * HW;
+  const _Float16* bias = head ? ops.bias[1] : ops.bias[0];
+
+  hd_partials<NT, NP, XT>(smem, part, src, head ? ops.wpack[1] : ops.wpack[0], y0, x0, H, W, HW);
+
+  const int ty = tid / HD_TX, tx = tid % HD_TX;
+  const int y = y0 + ty, xo = x0 + tx;
+  if (tid >= HD_TX * HD_TY || y >= H || xo >= W) return;
+  _Float16 h[2];
+#pragma unroll
+  for (int co = 0; co < 2; co++) {
+    float s = (float)bias[co];
+#pragma unroll
+    for (int t = 0; t < 9; t++) s += part[(t * 2 + co) * HD_PPITCH + (ty + t / 3) * HD_LW + tx + t % 3];
+    h[co] = (_Float16)s;
+  }
+  if (head) {
+#pragma unroll
+    for (int co = 0; co < 2; co++) h[co] = (_Float16)kg_sigmoid((float)h[co]);
+  }
+  const size_t pix = (size_t)n * HW + (size_t)y * W + xo;
+  void* outv = head ? ops.out[1] : ops.out[0];
+  if (F32) {
+    f32x2 v = f32x2{(float)h[0], (float)h[1]};
+    if (!head) {
+      const f32x2 c = reinterpret_cast<const f32x2*>(ops.coords)[pix];
+      v = f32x2{c[0] + v[0], c[1] + v[1]};
+    }
+    static_cast<f32x2*>(outv)[pix] = v;
+  } else {
+    static_cast<f16x2*>(outv)[pix] = f16x2{h[0], h[1]};
+  }
+}
+
+template <bool XH, bool F32>
+static int hd_pair_launch(const lgu_head_pair_args& a, int tiles_x, int tiles_y, int tiles, hipStream_t s) {
+  auto kern = head3x3_pair_c128_kernel<XH, F32>;
+  if (allow_max_dynamic_lds<head3x3_pair_c128_kernel<XH, F32>>() != hipSuccess) return launch_status();
+  HdPairOperands ops;
+  for (int k = 0; k < 2; k++) {
+    ops.x[k] = a.x[k];
+    ops.wpack[k] = static_cast<const f16x8*>(a.wpack[k]);
+    ops.bias[k] = static_cast<const _Float16*>(a.bias[k]);
+    ops.out[k] = a.out[k];
+  }
+  ops.coords = static_cast<const float*>(a.coords);
+  hipLaunchKernelGGL(kern, dim3(2u * (unsigned)tiles), dim3(HD_THREADS), hd_lds_bytes<2>(), s, ops, a.H, a.W, tiles_x, tiles_y,
+                     tiles);
   return launch_status();
 }
 
@@ -202,4 +293,27 @@ extern "C" int lgu_head3x3_c128_h16(lgu_head_args a, void* stream) {
   if (a.Cout == 2)
     return xh ? hd_launch_act<2, true>(a, (unsigned)blocks, tiles_x, tiles_y, s) : hd_launch_act<2, false>(a, (unsigned)blocks, tiles_x, tiles_y, s);
   return xh ? hd_launch_act<1, true>(a, (unsigned)blocks, tiles_x, tiles_y, s) : hd_launch_act<1, false>(a, (unsigned)blocks, tiles_x, tiles_y, s);
+}
+
+extern "C" int lgu_head3x3_pair_c128_h16(lgu_head_pair_args a, void* stream) {
+  using namespace lgu;
+  constexpr int kFlags = LGU_HEAD_X_HALF | LGU_HEAD_PAIR_F32;
+  if (a.N < 0 || a.H < 0 || a.W < 0 || (a.flags & ~kFlags)) return LGU_E_BADARG;
+  const bool xh = (a.flags & LGU_HEAD_X_HALF) != 0, f32 = (a.flags & LGU_HEAD_PAIR_F32) != 0;
+  if (f32 != (a.coords != nullptr)) return LGU_E_BADARG;      // the float32 mode is the one with coords
+  if (a.N == 0 || a.H == 0 || a.W == 0) return LGU_OK;
+  for (int k = 0; k < 2; k++) {
+    if (!a.x[k] || !a.wpack[k] || !a.bias[k] || !a.out[k]) return LGU_E_BADARG;
+    if (!hd_aligned(a.x[k], xh ? 2 : 4) || !hd_aligned(a.bias[k], 2) || !hd_aligned(a.out[k], f32 ? 4 : 2)) return LGU_E_BADARG;
+  }
+  if (f32 && !hd_aligned(a.coords, 4)) return LGU_E_BADARG;
+  for (int k = 0; k < 2; k++)      // a pixel's two channels are one store
+    if (!hd_aligned(a.wpack[k], 16) || !hd_aligned(a.out[k], f32 ? 8 : 4)) return LGU_E_UNSUPPORTED;
+  if (f32 && !hd_aligned(a.coords, 8)) return LGU_E_UNSUPPORTED;
+  const int tiles_x = (a.W - 1) / HD_TX + 1, tiles_y = (a.H - 1) / HD_TY + 1;
+  const long long tiles = (long long)a.N * tiles_x * tiles_y;
+  if (2 * tiles > INT_MAX) return LGU_E_UNSUPPORTED;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (f32) return xh ? hd_pair_launch<true, true>(a, tiles_x, tiles_y, (int)tiles, s) : hd_pair_launch<false, true>(a, tiles_x, tiles_y, (int)tiles, s);
+  return xh ? hd_pair_launch<true, false>(a, tiles_x, tiles_y, (int)tiles, s) : hd_pair_launch<false, false>(a, tiles_x, tiles_y, (int)tiles, s);
 }

@@ -37,6 +37,11 @@ PASSTHROUGH = ("GradientClip", "Identity")
 # forward beyond the two spreads (tools/prof_heads.py): Head sends such calls to the module.
 # 0: every measured shape class kept the fused path.
 MIN_FUSED_PIXELS = {1: 0, 2: 0}
+PAIR_F32 = 8                             # include/lgu_corr.h LGU_HEAD_PAIR_F32
+# The number of pixels N * H * W below which `head_pair` does not beat the two `head_conv3x3` launches and their edge-major
+# copies beyond the two spreads (tools/prof_outstage.py): UpdateOperator takes those below it.
+# 0: every measured shape class kept the pair, in both output modes.
+MIN_PAIR_PIXELS = 0
 
 
 def pack_head(weight, bias):
@@ -89,6 +94,50 @@ def head_conv3x3(x, wpack, bias_h, act="none"):
     args = _lib.HeadArgs(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), N, H, W, cout, flags)
     launch("lgu_head3x3_c128_h16", "head_conv3x3", x.device, args, _stream(x))
     return out
+
+
+def head_pair(d, w, pack_delta, pack_weight, coords=None):
+    """The reference's delta[2] and weight[2] + Sigmoid in one launch, edge-major: d and w (N,128,H,W), the same shape and
+    dtype (float32 or half), pack_delta and pack_weight (wpack, bias_h) of `pack_head` with Cout 2.
+
+    Without `coords`: (delta, weight), each a new (1,N,H,W,2) half tensor with the bits of
+    head_conv3x3(d, *pack_delta, act="none") and head_conv3x3(w, *pack_weight, act="sigmoid") behind the reference's
+    view / permute / [..., :2] / contiguous.
+    With `coords` (1,N,H,W,2) float32: (target, weight), each a new (1,N,H,W,2) float32 tensor, target = coords +
+    delta.float() (one fp32 add, coords read at that element only) and weight = weight.float(): what the factor graph
+    keeps."""
+    for t, name in ((d, "d"), (w, "w")):
+        if t.dim() != 4 or t.shape[1] != CIN:
+            raise RuntimeError("%s must be (N,%d,H,W), got %s" % (name, CIN, tuple(t.shape)))
+    check_shape([(w, "w")], d.shape)
+    named = [(d, "d"), (w, "w")]
+    for (wpack, bias_h), name in ((pack_delta, "pack_delta"), (pack_weight, "pack_weight")):
+        if wpack.numel() != WPACK_HALVES[2]:
+            raise RuntimeError("%s: wpack must hold %d halves (pack_head, Cout 2), got %s" % (name, WPACK_HALVES[2], tuple(wpack.shape)))
+        check_shape([(bias_h, name + ": bias_h")], (2,))
+        named += [(wpack, name + ": wpack"), (bias_h, name + ": bias_h")]
+    N, _, H, W = d.shape
+    if coords is not None:
+        check_shape([(coords, "coords")], (1, N, H, W, 2))
+        named.append((coords, "coords"))
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:2], d.dtype)
+    check_dtype(named[2:6], torch.float16)
+    check_dtype(named[6:], torch.float32)
+    check_no_grad("head_pair", named)
+    check_device(named)
+    odt = torch.float16 if coords is None else torch.float32
+    outs = tuple(torch.empty((1, N, H, W, 2), dtype=odt, device=d.device) for _ in range(2))
+    if outs[0].numel() == 0:
+        return outs
+    two = _lib._vp * 2
+    flags = (X_HALF if d.dtype == torch.float16 else 0) | (0 if coords is None else PAIR_F32)
+    args = _lib.HeadPairArgs(two(d.data_ptr(), w.data_ptr()), two(pack_delta[0].data_ptr(), pack_weight[0].data_ptr()),
+                             two(pack_delta[1].data_ptr(), pack_weight[1].data_ptr()), two(outs[0].data_ptr(), outs[1].data_ptr()),
+                             None if coords is None else coords.data_ptr(), N, H, W, flags)
+    launch("lgu_head3x3_pair_c128_h16", "head_pair", d.device, args, _stream(d))
+    return outs
 
 
 def eligible(m):

@@ -86,7 +86,16 @@ class UpdateOperator:
     gru_convs: the GRU's three convolutions on csrc/gruconv.hip (KanBiasGRU's `convs`).
     defer_upmask: the fifth result is the aggregated features (1,U,128,ht,wd) half that agg.upmask would have consumed, in
     place of the (1,U,576,ht,wd) mask, which is then not written; `upmask_packed()` gives the layer's packed weights for
-    upmask.upsample_from_net_.  `fused_calls` counts whole fused forwards, `module_calls` the others."""
+    upmask.upsample_from_net_.  `fused_calls` counts whole fused forwards, `module_calls` the others.
+
+    Behind the GRU, delta[0], weight[0] and (with ii) agg.conv1 are one conv3x3_fanout launch where num * ht * wd reaches
+    conv3.MIN_FANOUT_PIXELS, and delta[2] and weight[2] one head_pair launch that writes (1,num,ht,wd,2) directly where it
+    reaches heads.MIN_PAIR_PIXELS; below them the separate launches, with the same bits.  `fanout_calls` and `pair_calls`
+    count the two.
+    coords1 (keyword of the call): a (1,num,ht,wd,2) float32 tensor, the factor graph's coordinates.  The second and third
+    results are then `coords1 + delta.to(dtype=torch.float)` and `weight.to(dtype=torch.float)`, float32, what
+    FactorGraph.update and update_lowmem keep: written by head_pair's launch on the fused route, formed with torch from the
+    half results on every other route, the module's own included."""
 
     def __init__(self, update, gru_convs=False, defer_upmask=False):
         _check_stack(getattr(update, "corr_encoder", None), "corr_encoder", conv1.eligible, "Conv2d(1..224, 128, 1)")
@@ -104,13 +113,15 @@ class UpdateOperator:
         self._packs = _Packs()
         self._upmask_conv = upmask._parse(update.agg.upmask)
         self.fused_calls = 0
+        self.fanout_calls = 0
+        self.pair_calls = 0
         self.module_calls = 0
 
     def upmask_packed(self):
         """(wpack, bias_h) of agg.upmask for upmask.upsample_from_net_, cached."""
         return self._packs.of(self._upmask_conv, upmask.pack_upmask)
 
-    def _fused(self, net, inp, corr, flow, ii):
+    def _fused(self, net, inp, corr, flow, ii, coords1=None):
         ts = [net, inp, corr] + ([] if flow is None else [flow])
         if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 5 and t.dtype in FLOAT_OR_HALF for t in ts):
             return False
@@ -122,6 +133,12 @@ class UpdateOperator:
             return False
         if net.shape[1] == 0 or net.shape[3] * net.shape[4] == 0:
             return False
+        if coords1 is not None:      # the factor graph's coordinates: (1, num, ht, wd, 2) float32 on the same device
+            if not (isinstance(coords1, torch.Tensor) and coords1.dtype == torch.float32 and coords1.device == dev):
+                return False
+            if tuple(coords1.shape) != (1, net.shape[1], net.shape[3], net.shape[4], 2):
+                return False
+            ts = ts + [coords1]
         m = self.module
         if net.shape[2] != 128 or corr.shape[2] != m.corr_encoder[0].in_channels or (flow is not None and flow.shape[2] != 4):
             return False
@@ -130,11 +147,14 @@ class UpdateOperator:
             return False
         return fused_dtype(ts + params) == torch.float16
 
-    def __call__(self, net, inp, corr, flow=None, ii=None, jj=None):
+    def __call__(self, net, inp, corr, flow=None, ii=None, jj=None, coords1=None):
         m = self.module
-        if not self._fused(net, inp, corr, flow, ii):
+        if not self._fused(net, inp, corr, flow, ii, coords1):
             self.module_calls += 1
-            return type(m).forward(m, net, inp, corr, flow, ii, jj)
+            out = type(m).forward(m, net, inp, corr, flow, ii, jj)
+            if coords1 is None:
+                return out
+            return (out[0], coords1 + out[1].to(dtype=torch.float), out[2].to(dtype=torch.float)) + tuple(out[3:])
         _, num, _, ht, wd = net.shape
         packs = self._packs
         c3, hd = conv3.pack_conv3, heads.pack_head
@@ -149,13 +169,27 @@ class UpdateOperator:
         flow = conv3.conv3x3(flow, *packs.of(m.flow_encoder[2], c3), relu=True)
         net = self.gru(net, inp, corr, flow)
 
-        def to_edges(t):       # the reference's view / permute / [..., :2] / contiguous
-            return t.view(1, num, -1, ht, wd).permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+        # the trunk behind the GRU: delta[0], weight[0] and (with ii) agg.conv1 read the same x, in one launch where that
+        # was measured to win, else in one launch each.  Same bits either way.
         x = net.contiguous()
-        d = conv3.conv3x3(x, *packs.of(m.delta[0], c3), relu=True)
-        delta = to_edges(heads.head_conv3x3(d, *packs.of(m.delta[2], hd), act="none"))
-        w = conv3.conv3x3(x, *packs.of(m.weight[0], c3), relu=True)
-        weight = to_edges(heads.head_conv3x3(w, *packs.of(m.weight[2], hd), act="sigmoid"))
+        trunk = [m.delta[0], m.weight[0]] + ([] if ii is None else [m.agg.conv1])
+        if num * ht * wd >= conv3.MIN_FANOUT_PIXELS:
+            feats = conv3.conv3x3_fanout(x, [packs.of(c, c3) for c in trunk], relu=True)
+            self.fanout_calls += 1
+        else:
+            feats = [conv3.conv3x3(x, *packs.of(c, c3), relu=True) for c in trunk]
+        d, w = feats[0], feats[1]
+        if num * ht * wd >= heads.MIN_PAIR_PIXELS:
+            coords = None if coords1 is None else coords1.contiguous()
+            delta, weight = heads.head_pair(d, w, packs.of(m.delta[2], hd), packs.of(m.weight[2], hd), coords=coords)
+            self.pair_calls += 1
+        else:
+            def to_edges(t):       # the reference's view / permute / [..., :2] / contiguous
+                return t.view(1, num, -1, ht, wd).permute(0, 1, 3, 4, 2)[..., :2].contiguous()
+            delta = to_edges(heads.head_conv3x3(d, *packs.of(m.delta[2], hd), act="none"))
+            weight = to_edges(heads.head_conv3x3(w, *packs.of(m.weight[2], hd), act="sigmoid"))
+            if coords1 is not None:      # the factor graph's own two expressions
+                delta, weight = coords1 + delta.to(dtype=torch.float), weight.to(dtype=torch.float)
         net = net.view(1, num, -1, ht, wd)
         self.fused_calls += 1
         if ii is None:
@@ -164,8 +198,7 @@ class UpdateOperator:
         agg = m.agg
         uniq, ix = torch.unique(ii.to(net.device), return_inverse=True)
         U = uniq.shape[0]
-        a = conv3.conv3x3(x, *packs.of(agg.conv1, c3), relu=True)
-        a = aggregate.scatter_mean(a.view(1, num, 128, ht, wd), ix.contiguous(), dim=1, dim_size=U)
+        a = aggregate.scatter_mean(feats[2].view(1, num, 128, ht, wd), ix.contiguous(), dim=1, dim_size=U)
         a = conv3.conv3x3(a.view(U, 128, ht, wd), *packs.of(agg.conv2, c3), relu=True)
         eta = heads.head_conv3x3(a, *packs.of(agg.eta[0], hd), act="softplus").view(1, U, ht, wd)
         if self.defer_upmask:
