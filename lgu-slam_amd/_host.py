@@ -1,5 +1,7 @@
 """The host vocabulary of the operator layer, once: pointer and stream plumbing, the dtype names, the argument refusals,
-the launch, and what the module wrappers (FeatureEncoder, KanBiasGRU, FlowEncoder, ProximityFactors) share.
+the launch, and what the module wrappers share: the Conv2d predicate, the packed-weight cache (`PackCache`), the autocast /
+grad decision, the routing predicate of the half-only layers (`serves_half`), the route-and-count call of a single-layer
+wrapper (`LayerWrapper`: Conv1, Conv3, Head, Upmask, FlowEncoder), and bind / unbind / `installed` of a forward.
 
 Every refusal takes a list of (tensor, "name") pairs and raises the text the reference (or torch) raises for the same
 defect.  The ORDER in which an operator calls them is part of its behaviour (an argument with two defects reports the
@@ -148,6 +150,16 @@ def check_operands(pairs, dtype=None):
             raise RuntimeError("expected scalar type %s but found %s (%s)" % (spelled, bare_name(t.dtype), name))
 
 
+def check_layer_operands(what, named):
+    """What follows the shape checks of a half-only layer operator `what`: named[0] is x, float32 or half, the rest are
+    the packs, half."""
+    check_contiguous(named)
+    check_dtype(named[:1], FLOAT_OR_HALF)
+    check_dtype(named[1:], torch.float16)
+    check_no_grad(what, named)
+    check_device(named)
+
+
 # ---- what the module wrappers share ---------------------------------------------------------------------------------
 def is_conv(m, cin, cout, k, stride=1, pad=0, bias=None):
     """m is Conv2d(cin, cout, k, stride, pad) without dilation, groups or a padding mode; bias=True: and has a bias."""
@@ -161,6 +173,27 @@ def param_key(tensors):
     return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
 
 
+class PackCache:
+    """Packed weights, one entry per slot, each kept while the parameters it was made of are what they were (`param_key`):
+    load_state_dict, in-place updates and moves make a new pack, which replaces the slot's old one."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def get(self, slot, tensors, make, *extra):
+        """`make()`, cached under `slot` while (extra, param_key(tensors)) is unchanged."""
+        key = (extra, param_key(tensors))
+        hit = self._slots.get(slot)
+        if hit is None or hit[0] != key:
+            hit = (key, make())
+            self._slots[slot] = hit
+        return hit[1]
+
+    def of(self, conv, pack):
+        """pack(conv.weight, conv.bias), cached per layer."""
+        return self.get(id(conv), (conv.weight, conv.bias), lambda: pack(conv.weight, conv.bias))
+
+
 def fused_dtype(tensors):
     """The dtype a fused path computes in now: float16 under CUDA float16 autocast, float32 with autocast off; None (the
     module's own forward) under any other autocast, or when grad mode is on and one of `tensors` requires grad."""
@@ -169,6 +202,65 @@ def fused_dtype(tensors):
     if torch.is_autocast_enabled("cuda"):
         return torch.float16 if torch.get_autocast_dtype("cuda") == torch.float16 else None
     return torch.float32
+
+
+def serves_half(x, cin, params, min_pixels):
+    """The fused path of a layer that has a half kernel only serves this call: x is a HIP tensor (N,cin,H,W), float32 or
+    half, with a non-empty frame and at least `min_pixels` pixels N*H*W; `params` are float32 on x's device; CUDA float16
+    autocast is on and nothing requires grad.  (A batch of 0 is served: the operators return the empty result.)"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != cin:
+        return False
+    if x.dtype not in FLOAT_OR_HALF or x.shape[2] * x.shape[3] == 0:
+        return False
+    if any(p.dtype != torch.float32 or p.device != x.device for p in params):
+        return False
+    if fused_dtype([x, *params]) != torch.float16:      # there is no fp32 kernel
+        return False
+    return x.shape[0] * x.shape[2] * x.shape[3] >= min_pixels
+
+
+class LayerWrapper:
+    """Callable stand-in for the forward of `module`, whose layer `conv` has a fused half kernel.  A call the subclass's
+    `_serves(x)` admits is `_operator(x.contiguous(), *packed())`, counted in `fused_calls` once the operator has
+    returned, then `_finish`; every other call is the module's own forward, followed by a ReLU where `relu` is set.
+
+    A subclass checks its module, hands `conv` and its pack function to this constructor, and states `_serves` (one
+    `serves_half` with its Cin, the parameters it gates on and its module's MIN_FUSED_PIXELS, read at the call) and
+    `_operator` (its operator function)."""
+
+    relu = False
+
+    def __init__(self, module, conv, pack):
+        self.module = module
+        self.conv = conv
+        self._pack = pack
+        self._packs = PackCache()
+        self.fused_calls = 0
+
+    def packed(self):
+        """(wpack, bias_h) of `conv`, cached."""
+        return self._packs.of(self.conv, self._pack)
+
+    def _finish(self, y):
+        return y
+
+    def __call__(self, x):
+        m = self.module
+        if not self._serves(x):
+            y = type(m).forward(m, x)
+            return torch.relu(y) if self.relu else y
+        y = self._operator(x.contiguous(), *self.packed())
+        self.fused_calls += 1
+        return self._finish(y)
+
+
+def installed(module, classes, who, hint=""):
+    """The wrapper of `classes` that `module.forward` already carries; None if nothing is bound there (or `module` is no
+    nn.Module); a wrapper of any other kind is refused in the name of `who`."""
+    cur = module.__dict__.get("forward") if isinstance(module, torch.nn.Module) else None
+    if cur is None or isinstance(cur, classes):
+        return cur
+    raise RuntimeError("%s: forward already carries a %s%s" % (who, type(cur).__name__, hint))
 
 
 def bind(obj, attr, cls, make):

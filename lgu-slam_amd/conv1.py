@@ -17,8 +17,7 @@ There is no fp32 kernel: fp32 evaluation is the module's own forward.
 import torch
 
 from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
-                    is_conv, launch, param_key, unbind)
+from ._host import LayerWrapper, bind, check_layer_operands, check_shape, installed, is_conv, launch, serves_half, unbind
 from ._host import stream as _stream
 
 COUT = 128                    # include/lgu_corr.h LGU_CONV1_COUT
@@ -68,11 +67,7 @@ def conv1x1(x, wpack, bias_h, cin=None, relu=False):
         raise RuntimeError("wpack must hold %d halves (pack_conv1), got %s" % (WPACK_HALVES, tuple(wpack.shape)))
     named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
     check_shape(named[2:], (COUT,))
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("conv1x1", named)
-    check_device(named)
+    check_layer_operands("conv1x1", named)
     N, _, H, W = x.shape
     out = torch.empty((N, COUT, H, W), dtype=torch.float16, device=x.device)
     if N == 0:
@@ -90,56 +85,30 @@ def eligible(m):
     return isinstance(m, torch.nn.Conv2d) and 1 <= m.in_channels <= MAX_CIN and is_conv(m, m.in_channels, COUT, 1, pad=0, bias=True)
 
 
-def _serves(conv, x):
-    """The fused path applies to this call of an eligible `conv` on x."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != conv.in_channels:
-        return False
-    if x.dtype not in FLOAT_OR_HALF or x.shape[2] * x.shape[3] == 0:
-        return False
-    params = [conv.weight, conv.bias]
-    if any(p.dtype != torch.float32 or p.device != x.device for p in params):
-        return False
-    if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
-        return False
-    return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS
-
-
-class Conv1:
+class Conv1(LayerWrapper):
     """Callable stand-in for the forward of one Conv2d(1..224, 128, 1) with a bias:
 
         fused = Conv1(update_module.corr_encoder[0])
         y = fused(corr)                        # = update_module.corr_encoder[0](corr); relu=True: = relu(conv(corr))
 
     Fused path (csrc/conv1.hip, one launch) for a HIP tensor (N,Cin,H,W), float32 or half, under CUDA autocast with
-    float16, with float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS.
-    Everything else goes to the module's own forward unchanged (followed by relu if relu=True): CPU tensors, other
-    dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's weight and bias
-    (data pointer, version, device).  `fused_calls` counts the fused launches."""
+    float16, with float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS
+    (_host.serves_half).  Everything else goes to the module's own forward unchanged (followed by relu if relu=True): CPU
+    tensors, other dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's
+    weight and bias (data pointer, version, device).  `fused_calls` counts the fused launches."""
 
     def __init__(self, conv, relu=False):
         if not eligible(conv):
             raise RuntimeError("Conv1: the module must be Conv2d(1..%d, 128, 1) with a bias" % MAX_CIN)
-        self.module = conv
+        super().__init__(conv, conv, pack_conv1)
         self.relu = bool(relu)
-        self._pack = None
-        self.fused_calls = 0
 
-    def packed(self):
-        """(wpack, bias_h), cached."""
-        key = param_key((self.module.weight, self.module.bias))
-        if self._pack is None or self._pack[0] != key:
-            self._pack = (key, pack_conv1(self.module.weight, self.module.bias))
-        return self._pack[1]
+    def _serves(self, x):
+        c = self.conv
+        return serves_half(x, c.in_channels, (c.weight, c.bias), MIN_FUSED_PIXELS)
 
-    def __call__(self, x):
-        m = self.module
-        if not _serves(m, x):
-            y = type(m).forward(m, x)
-            return torch.relu(y) if self.relu else y
-        wpack, bias_h = self.packed()
-        y = conv1x1(x.contiguous(), wpack, bias_h, cin=m.in_channels, relu=self.relu)
-        self.fused_calls += 1
-        return y
+    def _operator(self, x, wpack, bias_h):
+        return conv1x1(x, wpack, bias_h, cin=self.conv.in_channels, relu=self.relu)
 
 
 def install(conv, relu=False):
@@ -149,12 +118,7 @@ def install(conv, relu=False):
 
     `install` goes on the Conv2d, corr_encoder[0]: a conv3.Conv3Stack on corr_encoder then reaches it "as itself", in
     either install order, and the Sequential's ReLU stays a launch of its own (update.UpdateOperator fuses it)."""
-    cur = conv.__dict__.get("forward") if isinstance(conv, torch.nn.Module) else None
-    if isinstance(cur, Conv1):
-        return cur
-    if cur is not None:
-        raise RuntimeError("conv1.install: forward already carries a %s" % type(cur).__name__)
-    return bind(conv, "forward", Conv1, lambda _: Conv1(conv, relu=relu))
+    return installed(conv, Conv1, "conv1.install") or bind(conv, "forward", Conv1, lambda _: Conv1(conv, relu=relu))
 
 
 def uninstall(conv):

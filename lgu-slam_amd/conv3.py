@@ -18,14 +18,15 @@ There is no fp32 kernel: fp32 evaluation is the module's own forward.
 import torch
 
 from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
-                    is_conv, launch, param_key, unbind)
+from ._host import (FLOAT_OR_HALF, LayerWrapper, PackCache, bind, check_layer_operands, check_shape, fused_dtype, installed,
+                    is_conv, launch, serves_half, unbind)
 from ._host import stream as _stream
 
 CIN = 128
 COUTS = (64, 128)
 # include/lgu_corr.h LGU_CONV3_WPACK_HALVES_<Cout> = 9 * 4 * (Cout / 16) * 64 * 8
 WPACK_HALVES = {64: 73728, 128: 147456}
+_COUT_OF_HALVES = {v: k for k, v in WPACK_HALVES.items()}
 X_HALF, RELU = 1, 2              # include/lgu_corr.h LGU_CONV3_X_HALF, LGU_CONV3_RELU
 
 # Per Cout, the number of output pixels N * H * W below which the measured fused layer does not beat the module's own
@@ -63,17 +64,13 @@ def conv3x3(x, wpack, bias_h, relu=False):
     UnsupportedShape."""
     if x.dim() != 4 or x.shape[1] != CIN:
         raise RuntimeError("x must be (N,%d,H,W), got %s" % (CIN, tuple(x.shape)))
-    cout = {v: k for k, v in WPACK_HALVES.items()}.get(wpack.numel())
+    cout = _COUT_OF_HALVES.get(wpack.numel())
     if cout is None:
         raise RuntimeError("wpack must hold %d or %d halves (pack_conv3), got %s"
                            % (WPACK_HALVES[64], WPACK_HALVES[128], tuple(wpack.shape)))
     named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
     check_shape(named[2:], (cout,))
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("conv3x3", named)
-    check_device(named)
+    check_layer_operands("conv3x3", named)
     N, _, H, W = x.shape
     out = torch.empty((N, cout, H, W), dtype=torch.float16, device=x.device)
     if N == 0:
@@ -103,11 +100,7 @@ def conv3x3_fanout(x, packs, relu=False):
                                % (g, WPACK_HALVES[128], tuple(wpack.shape)))
         check_shape([(bias_h, "packs[%d]: bias_h" % g)], (128,))
         named += [(wpack, "packs[%d]: wpack" % g), (bias_h, "packs[%d]: bias_h" % g)]
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("conv3x3_fanout", named)
-    check_device(named)
+    check_layer_operands("conv3x3_fanout", named)
     N, _, H, W = x.shape
     outs = tuple(torch.empty((N, 128, H, W), dtype=torch.float16, device=x.device) for _ in packs)
     if N == 0:
@@ -128,69 +121,34 @@ def eligible(m):
     return any(is_conv(m, CIN, cout, 3, pad=1, bias=True) for cout in COUTS)
 
 
-class _Packs:
-    """The packed weights of eligible convolutions, cached per layer under param_key((weight, bias)): load_state_dict,
-    in-place updates and moves are picked up."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def of(self, conv):
-        key = param_key((conv.weight, conv.bias))
-        hit = self._cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            hit = (key, pack_conv3(conv.weight, conv.bias))
-            self._cache[id(conv)] = hit
-        return hit[1]
-
-
 def _serves(conv, x):
     """The fused path applies to this call of an eligible `conv` on x."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != CIN:
-        return False
-    if x.dtype not in FLOAT_OR_HALF or x.shape[2] * x.shape[3] == 0:
-        return False
-    params = [conv.weight, conv.bias]
-    if any(p.dtype != torch.float32 or p.device != x.device for p in params):
-        return False
-    if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
-        return False
-    return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS[conv.out_channels]
+    return serves_half(x, CIN, (conv.weight, conv.bias), MIN_FUSED_PIXELS[conv.out_channels])
 
 
-class Conv3:
+class Conv3(LayerWrapper):
     """Callable stand-in for the forward of one Conv2d(128, 64 or 128, 3, padding=1) with a bias:
 
         fused = Conv3(update_module.agg.conv1)
         y = fused(net)                         # = update_module.agg.conv1(net); relu=True: = relu(conv(net))
 
     Fused path (csrc/conv3.hip) for a HIP tensor (N,128,H,W), float32 or half, under CUDA autocast with float16, with
-    float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS[Cout].
-    Everything else goes to the module's own forward unchanged (followed by relu if relu=True): CPU tensors, other
-    dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's weight and bias
-    (data pointer, version, device)."""
+    float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS[Cout]
+    (_host.serves_half).  Everything else goes to the module's own forward unchanged (followed by relu if relu=True): CPU
+    tensors, other dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's
+    weight and bias (data pointer, version, device).  `fused_calls` counts the fused launches."""
 
     def __init__(self, conv, relu=False):
         if not eligible(conv):
             raise RuntimeError("Conv3: the module must be Conv2d(128, 64 or 128, 3, padding=1) with a bias")
-        self.module = conv
+        super().__init__(conv, conv, pack_conv3)
         self.relu = bool(relu)
-        self._packs = _Packs()
-        self.fused_calls = 0
 
-    def packed(self):
-        """(wpack, bias_h), cached."""
-        return self._packs.of(self.module)
+    def _serves(self, x):
+        return _serves(self.conv, x)
 
-    def __call__(self, x):
-        m = self.module
-        if not _serves(m, x):
-            y = type(m).forward(m, x)
-            return torch.relu(y) if self.relu else y
-        wpack, bias_h = self.packed()
-        y = conv3x3(x.contiguous(), wpack, bias_h, relu=self.relu)
-        self.fused_calls += 1
-        return y
+    def _operator(self, x, wpack, bias_h):
+        return conv3x3(x, wpack, bias_h, relu=self.relu)
 
 
 class Conv3Stack:
@@ -212,7 +170,7 @@ class Conv3Stack:
             raise RuntimeError("Conv3Stack: the module must be an nn.Sequential that holds a Conv2d(128, 64 or 128, 3, "
                                "padding=1) with a bias")
         self.module = module
-        self._packs = _Packs()
+        self._packs = PackCache()
         self.fused_calls = 0
 
     def _fused(self, x):
@@ -230,7 +188,7 @@ class Conv3Stack:
             m = members[i]
             if eligible(m) and _serves(m, x):
                 relu = i + 1 < len(members) and isinstance(members[i + 1], torch.nn.ReLU)
-                wpack, bias_h = self._packs.of(m)
+                wpack, bias_h = self._packs.of(m, pack_conv3)
                 x = conv3x3(x.contiguous(), wpack, bias_h, relu=relu)
                 self.fused_calls += 1
                 i += 2 if relu else 1
@@ -248,12 +206,9 @@ def install(module, relu=False):
     an instance attribute: parameters and state_dict keys are unchanged.  Returns the wrapper; a second call returns the
     first wrapper.  Anything else raises RuntimeError and binds nothing, and so does a Sequential whose forward already
     carries another wrapper (install on its eligible member instead)."""
-    cur = module.__dict__.get("forward") if isinstance(module, torch.nn.Module) else None
-    if isinstance(cur, _WRAPPERS):
-        return cur
+    cur = installed(module, _WRAPPERS, "conv3.install", "; install on the eligible Conv2d inside it")
     if cur is not None:
-        raise RuntimeError("conv3.install: forward already carries a %s; install on the eligible Conv2d inside it"
-                           % type(cur).__name__)
+        return cur
     if isinstance(module, torch.nn.Conv2d):
         return bind(module, "forward", Conv3, lambda _: Conv3(module, relu=relu))
     if isinstance(module, torch.nn.Sequential):

@@ -15,8 +15,7 @@ mode is on.  There is no fp32 kernel: fp32 evaluation is the module's own forwar
 import torch
 
 from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
-                    is_conv, launch, param_key, unbind)
+from ._host import LayerWrapper, bind, check_layer_operands, check_shape, is_conv, launch, serves_half, unbind
 from ._host import stream as _stream
 
 CIN, COUT, KW, PAD, C2 = 4, 128, 7, 3, 64
@@ -55,11 +54,7 @@ def flow_conv7_relu(x, wpack, bias_h):
         raise RuntimeError("wpack must hold %d halves (pack_conv7), got %s" % (WPACK_HALVES, tuple(wpack.shape)))
     named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
     check_shape(named[2:], (COUT,))
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("flow_conv7_relu", named)
-    check_device(named)
+    check_layer_operands("flow_conv7_relu", named)
     N, _, H, W = x.shape
     out = torch.empty((N, COUT, H, W), dtype=torch.float16, device=x.device)
     if N == 0:
@@ -73,17 +68,18 @@ def flow_conv7_relu(x, wpack, bias_h):
     return out
 
 
-class FlowEncoder:
+class FlowEncoder(LayerWrapper):
     """Callable stand-in for the forward of the reference's `flow_encoder`:
 
         fused = FlowEncoder(update_module.flow_encoder)
         flow = fused(motn)                     # = update_module.flow_encoder(motn)
 
     Fused path (csrc/flowenc.hip + the module's second convolution) for a HIP tensor (N,4,H,W), float32 or half, under
-    CUDA autocast with float16, with float32 parameters on the input's device.  Everything else goes to the module's own
-    forward unchanged: CPU tensors, other dtypes, a bfloat16 autocast, autocast off, and grad mode with parameters or an
-    input that require grad.  The packed weights are cached; the key covers the first layer's weight and bias (data
-    pointer, version, device), so load_state_dict and in-place updates are picked up."""
+    CUDA autocast with float16, with float32 parameters (both convolutions') on the input's device and at least
+    MIN_FUSED_PIXELS pixels N*H*W (_host.serves_half).  Everything else goes to the module's own forward unchanged: CPU
+    tensors, other dtypes, a bfloat16 autocast, autocast off, and grad mode with parameters or an input that require grad.
+    The packed weights are cached; the key covers the first layer's weight and bias (data pointer, version, device), so
+    load_state_dict and in-place updates are picked up.  `fused_calls` counts the fused launches."""
 
     def __init__(self, module):
         ok = isinstance(module, torch.nn.Sequential) and len(module) == 4
@@ -92,39 +88,17 @@ class FlowEncoder:
         if not ok:
             raise RuntimeError("FlowEncoder: the module must be Sequential(Conv2d(4, 128, 7, padding=3), ReLU, "
                                "Conv2d(128, 64, 3, padding=1), ReLU) with biases")
-        self.module = module
-        self._key = None
-        self._packed = None
-        self.fused_calls = 0
+        super().__init__(module, module[0], pack_conv7)
 
-    def packed(self):
-        """(wpack, bias_h) of the first layer, cached."""
-        c1 = self.module[0]
-        key = param_key((c1.weight, c1.bias))
-        if key != self._key:
-            self._packed, self._key = pack_conv7(c1.weight, c1.bias), key
-        return self._packed
+    def _serves(self, x):
+        c1, c2 = self.conv, self.module[2]
+        return serves_half(x, CIN, (c1.weight, c1.bias, c2.weight, c2.bias), MIN_FUSED_PIXELS)
 
-    def _fused(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != CIN:
-            return False
-        if x.dtype not in (torch.float32, torch.float16) or x.shape[2] * x.shape[3] == 0:
-            return False
-        params = [self.module[0].weight, self.module[0].bias, self.module[2].weight, self.module[2].bias]
-        if any(p.dtype != torch.float32 or p.device != x.device for p in params):
-            return False
-        if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
-            return False
-        return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS
+    def _operator(self, x, wpack, bias_h):
+        return flow_conv7_relu(x, wpack, bias_h)
 
-    def __call__(self, x):
-        m = self.module
-        if not self._fused(x):
-            return type(m).forward(m, x)
-        wpack, bias_h = self.packed()
-        y = flow_conv7_relu(x.contiguous(), wpack, bias_h)
-        self.fused_calls += 1
-        return torch.relu_(m[2](y))
+    def _finish(self, y):
+        return torch.relu_(self.module[2](y))
 
 
 def install(module):

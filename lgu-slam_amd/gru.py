@@ -20,8 +20,8 @@ float16 tensors the half kernels with the reference's autocast rounding points (
 import torch
 
 from . import _lib
-from ._host import (bind, check_contiguous, check_device, check_dtype, check_no_grad, check_same_dtype, check_shape, fused_dtype,
-                    is_conv, launch, param_key, typed, unbind)
+from ._host import (PackCache, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_same_dtype, check_shape,
+                    fused_dtype, is_conv, launch, typed, unbind)
 from ._host import ptr as _ptr, stream as _stream
 
 C, CIN, NKNOT, NBASIS = 128, 448, 10, 6
@@ -32,6 +32,7 @@ CONVS = ("convz", "convr", "convq")
 # include/lgu_corr.h LGU_GRUCONV_*: 126 K steps x Cout/16 channel tiles x 64 lanes x 8 halves
 GRUCONV_STEPS, MAX_SEGMENTS = 126, 4
 GRUCONV_WPACK_HALVES = {128: 516096, 256: 1032192}
+_COUT_OF_HALVES = {v: k for k, v in GRUCONV_WPACK_HALVES.items()}
 PLAIN, ZR, Q = 0, 1, 2
 
 # The number of pixels E * H * W below which a `convs=True` call takes the convs=False path: the smallest measured shape
@@ -167,7 +168,7 @@ def _gruconv(what, mode, segments, wpack, bias_h, couts, extra, like):
         raise RuntimeError("%s: the segments' channels must sum to %d, got %s" % (what, CIN, [t.shape[1] for t in segments]))
     for t, name, tail in extra:
         check_shape([(t, name)], (E,) + tuple(H if d == "H" else W if d == "W" else d for d in tail))
-    cout = {v: k for k, v in GRUCONV_WPACK_HALVES.items()}.get(wpack.numel())
+    cout = _COUT_OF_HALVES.get(wpack.numel())
     if cout not in couts:
         raise RuntimeError("wpack must hold %s halves (pack_gruconv), got %s"
                            % (" or ".join(str(GRUCONV_WPACK_HALVES[c]) for c in couts), tuple(wpack.shape)))
@@ -279,12 +280,9 @@ class KanBiasGRU:
         for name in HEADS:
             _check_kan(getattr(module, name, None), name)
         self.module = module
-        self._key = None
-        self._packed = None
+        self._packs = PackCache()
         self.fused_calls = 0
         self.convs = bool(convs)
-        self._conv_key = None
-        self._conv_packed = None
         self.fused_conv_calls = 0
 
     def _sources(self):
@@ -297,25 +295,21 @@ class KanBiasGRU:
 
     def packed(self, dtype):
         """(w (128,128), b (128), grid (3,128,10), wpack (384,896)) for the kernels in `dtype`, cached."""
-        ts = self._sources()
-        key = (dtype,) + param_key(ts)
-        if key != self._key:
-            m = self.module
+        m = self.module
+
+        def make():
             with torch.no_grad():
                 w = m.w.weight.detach().reshape(C, C).to(dtype).contiguous()
                 b = m.w.bias.detach().to(dtype).contiguous()
-                grid, wpack = pack_heads([getattr(m, n) for n in HEADS], dtype)
-            self._packed, self._key = (w, b, grid, wpack), key
-        return self._packed
+                return (w, b) + pack_heads([getattr(m, n) for n in HEADS], dtype)
+        return self._packs.get("heads", self._sources(), make, dtype)
 
     def conv_packed(self):
         """((wpack_zr, bias_zr), (wpack_q, bias_q)) for gru_conv_zr and gru_conv_q, cached under the three convolutions'
         weights and biases."""
         m = self.module
-        key = param_key([p for n in CONVS for p in (getattr(m, n).weight, getattr(m, n).bias)])
-        if key != self._conv_key:
-            self._conv_packed, self._conv_key = (pack_gruconv((m.convz, m.convr)), pack_gruconv(m.convq)), key
-        return self._conv_packed
+        return self._packs.get("convs", [p for n in CONVS for p in (getattr(m, n).weight, getattr(m, n).bias)],
+                               lambda: (pack_gruconv((m.convz, m.convr)), pack_gruconv(m.convq)))
 
     def _mode(self, net, inputs):
         """torch.float16 / torch.float32 for the fused path, None for the module's forward."""

@@ -20,14 +20,15 @@ is on.  There is no fp32 kernel: fp32 evaluation is the module's own forward.
 import torch
 
 from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
-                    is_conv, launch, param_key, unbind)
+from ._host import (FLOAT_OR_HALF, LayerWrapper, bind, check_contiguous, check_device, check_dtype, check_layer_operands,
+                    check_no_grad, check_shape, installed, is_conv, launch, serves_half, unbind)
 from ._host import stream as _stream
 
 CIN = 128
 COUTS = (1, 2)
 # include/lgu_corr.h LGU_HEAD_WPACK_HALVES_<Cout> = 4 * ceil(9 * Cout / 16) * 64 * 8
 WPACK_HALVES = {1: 2048, 2: 4096}
+_COUT_OF_HALVES = {v: k for k, v in WPACK_HALVES.items()}
 X_HALF, SIGMOID, SOFTPLUS = 1, 2, 4      # include/lgu_corr.h LGU_HEAD_X_HALF, LGU_HEAD_SIGMOID, LGU_HEAD_SOFTPLUS
 ACTS = {"none": 0, "sigmoid": SIGMOID, "softplus": SOFTPLUS}
 # type names of the members a tail may hold between its convolution and its activation: their forward is the identity
@@ -75,17 +76,13 @@ def head_conv3x3(x, wpack, bias_h, act="none"):
         raise RuntimeError("act must be one of 'none', 'sigmoid', 'softplus', got %r" % (act,))
     if x.dim() != 4 or x.shape[1] != CIN:
         raise RuntimeError("x must be (N,%d,H,W), got %s" % (CIN, tuple(x.shape)))
-    cout = {v: k for k, v in WPACK_HALVES.items()}.get(wpack.numel())
+    cout = _COUT_OF_HALVES.get(wpack.numel())
     if cout is None:
         raise RuntimeError("wpack must hold %d or %d halves (pack_head), got %s"
                            % (WPACK_HALVES[1], WPACK_HALVES[2], tuple(wpack.shape)))
     named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
     check_shape(named[2:], (cout,))
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("head_conv3x3", named)
-    check_device(named)
+    check_layer_operands("head_conv3x3", named)
     N, _, H, W = x.shape
     out = torch.empty((N, cout, H, W), dtype=torch.float32 if act == "softplus" else torch.float16, device=x.device)
     if out.numel() == 0:
@@ -145,7 +142,7 @@ def eligible(m):
     return any(is_conv(m, CIN, cout, 3, pad=1, bias=True) for cout in COUTS)
 
 
-def _parse(module):
+def parse(module):
     """(conv, act) of an eligible Conv2d or of a tail Sequential [eligible conv, PASSTHROUGH members..., at most one final
     Sigmoid or Softplus(beta=1, threshold=20)]; None for anything else."""
     nn = torch.nn
@@ -165,7 +162,7 @@ def _parse(module):
     return module[0], act
 
 
-class Head:
+class Head(LayerWrapper):
     """Callable stand-in for the forward of one Conv2d(128, 1 or 2, 3, padding=1) with a bias, or of a "tail"
     nn.Sequential that is exactly [such a convolution, zero or more members whose type name is in PASSTHROUGH, at most
     one final nn.Sigmoid or nn.Softplus(beta=1, threshold=20)] (the reference's GraphAgg.eta):
@@ -175,49 +172,27 @@ class Head:
 
     Fused path (csrc/heads.hip, one launch with the activation in it) for a HIP tensor (N,128,H,W), float32 or half,
     under CUDA autocast with float16, with float32 parameters on the input's device, when nothing requires grad and
-    N*H*W >= MIN_FUSED_PIXELS[Cout].  The result has the module's own dtype there: half, or float32 behind a Softplus
-    (which autocast evaluates in float32).  Everything else goes to the module's own forward unchanged: CPU tensors,
-    other dtypes, a bfloat16 autocast, autocast off, and grad.  The packed weights are cached under the layer's weight
-    and bias (data pointer, version, device).  `fused_calls` counts the fused launches."""
+    N*H*W >= MIN_FUSED_PIXELS[Cout] (_host.serves_half; the convolution's weight and bias are all the parameters a tail
+    has).  The result has the module's own dtype there: half, or float32 behind a Softplus (which autocast evaluates in
+    float32).  Everything else goes to the module's own forward unchanged: CPU tensors, other dtypes, a bfloat16 autocast,
+    autocast off, and grad.  The packed weights are cached under the layer's weight and bias (data pointer, version,
+    device).  `fused_calls` counts the fused launches."""
 
     def __init__(self, module):
-        parsed = _parse(module)
+        parsed = parse(module)
         if parsed is None:
             raise RuntimeError("Head: the module must be Conv2d(128, 1 or 2, 3, padding=1) with a bias, or an nn.Sequential of "
                                "such a convolution, members named %s and at most one final Sigmoid or Softplus(beta=1, "
                                "threshold=20)" % " or ".join(PASSTHROUGH))
-        self.module = module
-        self.conv, self.act = parsed
-        self._pack = None
-        self.fused_calls = 0
-
-    def packed(self):
-        """(wpack, bias_h), cached."""
-        key = param_key((self.conv.weight, self.conv.bias))
-        if self._pack is None or self._pack[0] != key:
-            self._pack = (key, pack_head(self.conv.weight, self.conv.bias))
-        return self._pack[1]
+        super().__init__(module, parsed[0], pack_head)
+        self.act = parsed[1]
 
     def _serves(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != CIN:
-            return False
-        if x.dtype not in FLOAT_OR_HALF or x.shape[2] * x.shape[3] == 0:
-            return False
-        params = list(self.module.parameters())
-        if any(p.dtype != torch.float32 or p.device != x.device for p in params):
-            return False
-        if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
-            return False
-        return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS[self.conv.out_channels]
+        c = self.conv
+        return serves_half(x, CIN, (c.weight, c.bias), MIN_FUSED_PIXELS[c.out_channels])
 
-    def __call__(self, x):
-        m = self.module
-        if not self._serves(x):
-            return type(m).forward(m, x)
-        wpack, bias_h = self.packed()
-        y = head_conv3x3(x.contiguous(), wpack, bias_h, act=self.act)
-        self.fused_calls += 1
-        return y
+    def _operator(self, x, wpack, bias_h):
+        return head_conv3x3(x, wpack, bias_h, act=self.act)
 
 
 def install(module):
@@ -228,12 +203,7 @@ def install(module):
     Through `install` the Sigmoid of the reference's `weight` stays a launch of its own: `install` goes on weight[2], the
     Conv2d, because a wrapper that owned the whole `weight` Sequential would collide with conv3's Conv3Stack on it.  Only
     a tail that is a Sequential of its own (agg.eta) gets its activation fused."""
-    cur = module.__dict__.get("forward") if isinstance(module, torch.nn.Module) else None
-    if isinstance(cur, Head):
-        return cur
-    if cur is not None:
-        raise RuntimeError("heads.install: forward already carries a %s" % type(cur).__name__)
-    return bind(module, "forward", Head, lambda _: Head(module))
+    return installed(module, Head, "heads.install") or bind(module, "forward", Head, lambda _: Head(module))
 
 
 def uninstall(module):
@@ -252,7 +222,7 @@ def install_update(update):
     as themselves.  Refuses before anything is bound if a site does not match.  Returns {site name: wrapper}."""
     sites = _sites(update)
     for name, m in sites:       # refuse before anything is bound
-        parsed = _parse(m)
+        parsed = parse(m)
         want_tail = name == "agg.eta"
         ok = parsed is not None and isinstance(m, torch.nn.Sequential) == want_tail and (not want_tail or parsed[1] == "softplus")
         if not ok:

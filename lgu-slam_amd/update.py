@@ -14,23 +14,7 @@ Forward only; batch 1; not graph-capturable with `ii` given (torch.unique reads 
 import torch
 
 from . import aggregate, conv1, conv3, flow as _flow, gru as _gru, heads, upmask
-from ._host import FLOAT_OR_HALF, fused_dtype, param_key, unbind
-
-
-class _Packs:
-    """Packed weights of convolutions, cached per layer under param_key((weight, bias)): load_state_dict, in-place updates
-    and moves are picked up."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def of(self, conv, pack):
-        key = param_key((conv.weight, conv.bias))
-        hit = self._cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            hit = (key, pack(conv.weight, conv.bias))
-            self._cache[id(conv)] = hit
-        return hit[1]
+from ._host import FLOAT_OR_HALF, PackCache, bind, fused_dtype, installed, unbind
 
 
 def _refuse(site, want):
@@ -50,7 +34,7 @@ def _check_head_stack(m, site, act):
     nn = torch.nn
     ok = isinstance(m, nn.Sequential) and len(m) >= 3 and conv3.eligible(m[0]) and m[0].out_channels == 128
     ok = ok and isinstance(m[1], nn.ReLU)
-    parsed = heads._parse(m[2:]) if ok else None
+    parsed = heads.parse(m[2:]) if ok else None
     if parsed is None or parsed[0].out_channels != 2 or parsed[1] != act:
         _refuse(site, "Sequential(Conv2d(128, 128, 3, padding=1), ReLU, Conv2d(128, 2, 3, padding=1), pass-through members%s)"
                 % (", Sigmoid" if act == "sigmoid" else ""))
@@ -61,10 +45,10 @@ def _check_agg(agg):
         c = getattr(agg, name, None)
         if not (conv3.eligible(c) and c.out_channels == 128):
             _refuse("agg." + name, "Conv2d(128, 128, 3, padding=1) with a bias")
-    parsed = heads._parse(getattr(agg, "eta", None))
+    parsed = heads.parse(getattr(agg, "eta", None))
     if parsed is None or parsed[0].out_channels != 1 or parsed[1] != "softplus" or not isinstance(agg.eta, torch.nn.Sequential):
         _refuse("agg.eta", "Sequential(Conv2d(128, 1, 3, padding=1), pass-through members, Softplus)")
-    if upmask._parse(getattr(agg, "upmask", None)) is None:
+    if upmask.parse(getattr(agg, "upmask", None)) is None:
         _refuse("agg.upmask", "Conv2d(128, 576, 1) with a bias, or a Sequential holding exactly that")
 
 
@@ -110,8 +94,8 @@ class UpdateOperator:
         self.gru = _gru.KanBiasGRU(getattr(update, "gru", None), convs=gru_convs)   # raises unless KAN_bias_GRU(128, 320)
         self.module = update
         self.defer_upmask = bool(defer_upmask)
-        self._packs = _Packs()
-        self._upmask_conv = upmask._parse(update.agg.upmask)
+        self._packs = PackCache()
+        self._upmask_conv = upmask.parse(update.agg.upmask)
         self.fused_calls = 0
         self.fanout_calls = 0
         self.pair_calls = 0
@@ -212,16 +196,12 @@ def install(update, gru_convs=False, defer_upmask=False):
     unchanged, and nothing is bound on a submodule.  Returns the wrapper; a second call returns the first wrapper with
     the flags set as given.  A module that is not shaped like the reference's raises RuntimeError and binds nothing, and
     so does a module whose forward already carries another wrapper."""
-    cur = update.__dict__.get("forward") if isinstance(update, torch.nn.Module) else None
-    if isinstance(cur, UpdateOperator):
+    cur = installed(update, UpdateOperator, "update.install")
+    if cur is not None:
         cur.gru.convs = bool(gru_convs)
         cur.defer_upmask = bool(defer_upmask)
         return cur
-    if cur is not None:
-        raise RuntimeError("update.install: forward already carries a %s" % type(cur).__name__)
-    wrapper = UpdateOperator(update, gru_convs=gru_convs, defer_upmask=defer_upmask)
-    update.forward = wrapper
-    return wrapper
+    return bind(update, "forward", UpdateOperator, lambda _: UpdateOperator(update, gru_convs=gru_convs, defer_upmask=defer_upmask))
 
 
 def uninstall(update):

@@ -18,8 +18,8 @@ no fp32 kernel: fp32 evaluation is the module's own forward.
 import torch
 
 from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, fused_dtype,
-                    is_conv, launch, param_key, unbind)
+from ._host import (FLOAT_OR_HALF, LayerWrapper, bind, check_contiguous, check_device, check_dtype, check_layer_operands,
+                    check_no_grad, check_shape, installed, is_conv, launch, serves_half, unbind)
 from ._host import stream as _stream
 
 CIN = 128
@@ -63,11 +63,7 @@ def upmask_conv1x1(x, wpack, bias_h):
     what pack_upmask returns) raises UnsupportedShape."""
     _check_net(x, wpack, bias_h)
     named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
-    check_contiguous(named)
-    check_dtype(named[:1], FLOAT_OR_HALF)
-    check_dtype(named[1:], torch.float16)
-    check_no_grad("upmask_conv1x1", named)
-    check_device(named)
+    check_layer_operands("upmask_conv1x1", named)
     N, _, H, W = x.shape
     out = torch.empty((N, COUT, H, W), dtype=torch.float16, device=x.device)
     if out.numel() == 0:
@@ -123,7 +119,7 @@ def eligible(m):
     return is_conv(m, CIN, COUT, 1, pad=0, bias=True)
 
 
-def _parse(module):
+def parse(module):
     """The convolution of an eligible Conv2d or of a Sequential holding exactly one; None for anything else."""
     if eligible(module):
         return module
@@ -132,7 +128,7 @@ def _parse(module):
     return None
 
 
-class Upmask:
+class Upmask(LayerWrapper):
     """Callable stand-in for the forward of a Conv2d(128, 576, 1) with a bias, or of an nn.Sequential holding exactly that
     (the reference's GraphAgg.upmask):
 
@@ -140,60 +136,35 @@ class Upmask:
         mask = fused(net)                      # = update_module.agg.upmask(net)
 
     Fused path (csrc/upmask.hip, one launch) for a HIP tensor (N,128,H,W), float32 or half, under CUDA autocast with
-    float16, with float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS.
-    Everything else goes to the module's own forward unchanged: CPU tensors, other dtypes, a bfloat16 autocast, autocast
-    off, and grad.  The packed weights are cached under the layer's weight and bias (data pointer, version, device);
-    `packed()` returns them for `upsample_from_net_`.  `fused_calls` counts the fused launches."""
+    float16, with float32 parameters on the input's device, when nothing requires grad and N*H*W >= MIN_FUSED_PIXELS
+    (_host.serves_half).  Everything else goes to the module's own forward unchanged: CPU tensors, other dtypes, a
+    bfloat16 autocast, autocast off, and grad.  Unlike the other single-layer wrappers, Upmask also sends a batch of 0
+    (N == 0) to the module: a rule of its own, stated in `_serves`, where the others hand it to their operator.  The
+    packed weights are cached under the layer's weight and bias (data pointer, version, device); `packed()` returns them
+    for `upsample_from_net_`.  `fused_calls` counts the fused launches."""
 
     def __init__(self, module):
-        conv = _parse(module)
+        conv = parse(module)
         if conv is None:
             raise RuntimeError("Upmask: the module must be Conv2d(128, 576, 1) with a bias, or an nn.Sequential holding "
                                "exactly that")
-        self.module = module
-        self.conv = conv
-        self._pack = None
-        self.fused_calls = 0
-
-    def packed(self):
-        """(wpack, bias_h), cached."""
-        key = param_key((self.conv.weight, self.conv.bias))
-        if self._pack is None or self._pack[0] != key:
-            self._pack = (key, pack_upmask(self.conv.weight, self.conv.bias))
-        return self._pack[1]
+        super().__init__(module, conv, pack_upmask)
 
     def _serves(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != CIN:
+        if isinstance(x, torch.Tensor) and x.numel() == 0:      # N == 0 included: the module's
             return False
-        if x.dtype not in FLOAT_OR_HALF or x.numel() == 0:
-            return False
-        params = [self.conv.weight, self.conv.bias]
-        if any(p.dtype != torch.float32 or p.device != x.device for p in params):
-            return False
-        if fused_dtype([x] + params) != torch.float16:      # there is no fp32 kernel
-            return False
-        return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_FUSED_PIXELS
+        c = self.conv
+        return serves_half(x, CIN, (c.weight, c.bias), MIN_FUSED_PIXELS)
 
-    def __call__(self, x):
-        m = self.module
-        if not self._serves(x):
-            return type(m).forward(m, x)
-        wpack, bias_h = self.packed()
-        y = upmask_conv1x1(x.contiguous(), wpack, bias_h)
-        self.fused_calls += 1
-        return y
+    def _operator(self, x, wpack, bias_h):
+        return upmask_conv1x1(x, wpack, bias_h)
 
 
 def install(module):
     """Bind an Upmask as `module.forward`, an instance attribute: parameters and state_dict keys are unchanged.  Returns
     the wrapper; a second call returns the first wrapper.  A module Upmask does not take raises RuntimeError and binds
     nothing, and so does a module whose forward already carries another wrapper."""
-    cur = module.__dict__.get("forward") if isinstance(module, torch.nn.Module) else None
-    if isinstance(cur, Upmask):
-        return cur
-    if cur is not None:
-        raise RuntimeError("upmask.install: forward already carries a %s" % type(cur).__name__)
-    return bind(module, "forward", Upmask, lambda _: Upmask(module))
+    return installed(module, Upmask, "upmask.install") or bind(module, "forward", Upmask, lambda _: Upmask(module))
 
 
 def uninstall(module):
