@@ -120,10 +120,64 @@ def generate_offsets(ofsMap, ofs_residual, feats, num_levels):
     are zero by construction.  Returned channel-last: list of (E,h,w,2*rd*rd) tensors, and
     a list of flags marking the structurally-zero levels.
     """
-    _, _, h, w = feats.shape
+    heads = _autocast_heads_on_matrix_cores(ofsMap, ofs_residual, feats)
+    if heads is not None:
+        return finish_offsets(heads[0], heads[1], num_levels)
     o0 = ofsMap(feats)
     o1_low = ofs_residual(F.avg_pool2d(feats, kernel_size=2, stride=2))
     return finish_offsets(o0, o1_low, num_levels)
+
+
+HALF_HEADS_ON_MATRIX_CORES = True   # False: the library's half convolution for the offset heads under autocast (A/B and tests)
+
+
+def _servable_head(conv, C2):
+    return (isinstance(conv, torch.nn.Conv2d) and conv.bias is not None and conv.in_channels == C2 and conv.out_channels <= 112
+            and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.stride == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros" and conv.weight.dtype in (torch.float32, torch.float16)
+            and not (torch.is_grad_enabled() and (conv.weight.requires_grad or conv.bias.requires_grad)))
+
+
+def _half_pack(conv):
+    """Operands of ops.offset_conv_frames for a head as float16 autocast evaluates it: weight and bias rounded to half,
+    kept on the module and remade when its parameters change."""
+    params = [conv.weight, conv.bias]
+    kept = getattr(conv, "_lgu_half_pack", None)
+    if kept is None or not kept[0].matches(params):
+        kept = (_Snapshot(params), ops.pack_offset_conv(conv.weight.detach().half().float(), conv.bias.detach().half().float(),
+                                                        scale=1.0))
+        conv._lgu_half_pack = kept
+    return kept[1]
+
+
+def _autocast_heads_on_matrix_cores(ofsMap, ofs_residual, feats):
+    """(ofsMap(feats), ofs_residual(avg_pool2d(feats))) for HALF maps inside float16 autocast — CorrBlock as add_factors
+    builds it (reference factor_graph.py:90, corr.py:120-122) — as a half convolution that accumulates in fp32 and rounds
+    ONCE gives them: ops.offset_conv_frames on the weights rounded to half, its fp32 result rounded to half.  The library's
+    half convolution on this device is not that: it leaves the correctly rounded value at two entries in three, by 1.6
+    half ulp on average and up to 2^-8 at |x| ~ 3, and differently from run to run, which 4 * tanh(x / std) carries into
+    the level-0 offsets as up to 1e-2 — more than twice what the reference's own half run moves them by
+    (tests/test_glue_autocast.py).  None: not this case, or a shape the kernel does not serve; the caller convolves."""
+    if not (HALF_HEADS_ON_MATRIX_CORES and FUSED_OFFSETS and feats.is_cuda and feats.dtype == torch.float16 and feats.dim() == 4
+            and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16
+            and not (torch.is_grad_enabled() and feats.requires_grad)):
+        return None
+    E, C2, h, w = feats.shape
+    if C2 % 64 != 0 or E == 0 or h < 2 or w < 2 or not (_servable_head(ofsMap, C2) and _servable_head(ofs_residual, C2)):
+        return None
+    try:
+        packs = _half_pack(ofsMap), _half_pack(ofs_residual)
+        ii = torch.arange(E, device=feats.device)
+        jj = ii + E
+        out = []
+        # the residual head's input is pooled in half, as avg_pool2d of the half maps is under autocast (corr.py:121)
+        for x, pack in ((feats, packs[0]), (F.avg_pool2d(feats, kernel_size=2, stride=2), packs[1])):
+            # the pair (E, 2C, h, w) as 2E channel-last frames: source maps first, target maps behind them
+            frames = x.reshape(E, 2, C2 // 2, x.shape[2], x.shape[3]).permute(1, 0, 3, 4, 2).reshape(2 * E, x.shape[2], x.shape[3], C2 // 2)
+            out.append(ops.offset_conv_frames(frames.contiguous(), ii, jj, pack).half())
+        return out
+    except _lib.UnsupportedShape:
+        return None
 
 
 def finish_offsets(o0, o1_low, num_levels, probe=None):

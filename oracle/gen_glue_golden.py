@@ -25,8 +25,13 @@ convolution / linear outputs caught by forward hooks (so a test can separate "sa
 given the same head outputs" from end-to-end agreement), offsets before / after each call,
 pyramid levels, mean_n, theta and every returned tensor.
 
+The CorrBlock scenario is also run in the reference's production mode, float16 autocast on the half maps
+(corrblock_autocast_scenario under cuda_autocast_on_cpu, with the audit of the CPU / GPU autocast policies that
+justifies running it on a CPU): glue_corrblock_autocast_16x16_*.npz and glue_autocast_policy.json.
+
     python oracle/gen_glue_golden.py [outdir=tests/golden]
 """
+import contextlib
 import os
 import sys
 import types
@@ -35,6 +40,7 @@ sys.dont_write_bytecode = True
 
 import numpy as np
 import torch
+from torch.utils._python_dispatch import TorchDispatchMode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
@@ -58,12 +64,20 @@ def _out(arrs):
     return [torch.from_numpy(a) for a in arrs]
 
 
+_gauss_calls = None   # a list while a scenario wants the (means, covs) the reference hands to defCorrSample.gaussianMask
+
+
 def make_stub_modules():
     from oracle import oracle as O
     O.build()
     d = types.ModuleType("defCorrSample")
-    d.gaussianMask = lambda means, covs, volume, radius: _out(
-        O.gaussianMask(_arr("means", means), _arr("covs", covs), _arr("volume", volume), int(radius)))
+
+    def gaussianMask(means, covs, volume, radius):
+        if _gauss_calls is not None:
+            _gauss_calls.append((means.detach().clone(), covs.detach().clone()))
+        return _out(O.gaussianMask(_arr("means", means), _arr("covs", covs), _arr("volume", volume), int(radius)))
+
+    d.gaussianMask = gaussianMask
     d.gaussianMask_backward = lambda means, covs, volume, volume_grad, radius: _out(
         O.gaussianMask_backward(_arr("means", means), _arr("covs", covs), _arr("volume", volume),
                                 _arr("volume_grad", volume_grad), int(radius)))
@@ -247,6 +261,210 @@ def corrblock_scenario(h, w, E_a, E_b, seed, sub=None):
     return out
 
 
+# ----------------------------------------------------------------------------- the reference's production mode: half autocast
+# factor_graph.py decorates add_factors / rm_factors / update with autocast(enabled=True) and video.fmaps is half, so the
+# reference builds and calls CorrBlock inside float16 autocast ON THE GPU.  This machine has CPUs only.  CPU and GPU autocast
+# cast the same operators of the glue, with one exception: nearest upsampling (F.interpolate, corr.py:124) carries an
+# AutocastCUDA kernel (run in fp32) and no AutocastCPU kernel (stays half).  `cuda_autocast_on_cpu` emulates that one
+# operator's GPU policy; `autocast_policy` audits, from the dispatcher's own tables, that no other operator the glue
+# executes differs between the two.
+EMULATED_OPS = ("aten::upsample_nearest2d",)
+# Two more operators differ in the tables and are recorded, not emulated, because the cast is the identity wherever the glue
+# meets them, which OpRecorder checks on every call:
+#   aten::cat          cast on the CPU only (to the widest input type; the GPU operator promotes by itself): the glue only
+#                      concatenates tensors of ONE dtype (the two half maps, the fp32 lookups, like offsets of two blocks);
+#   aten::convolution  cast on the GPU only (to half): it runs below aten::conv2d, which is cast on both devices, so its
+#                      operands are half already.
+INERT_OPS = {"aten::cat": None, "aten::convolution": torch.float16}   # name -> the one dtype its tensors must have (None: any)
+COMPOSITE_ENTRY_POINTS = ("aten::matmul", "aten::conv2d", "aten::linear")   # what the glue's text calls; a dispatch mode sees
+                                                                            # only what they decompose into
+
+
+@contextlib.contextmanager
+def cuda_autocast_on_cpu():
+    """torch.autocast("cpu", float16) with the GPU's policy for F.interpolate: a half input is up-sampled in fp32 with
+    autocast off (what AutocastCUDA's fp32 cast policy does), anything else goes to the real function."""
+    import torch.nn.functional as F
+    real = F.interpolate
+
+    def interpolate(input, *args, **kwargs):
+        if isinstance(input, torch.Tensor) and input.dtype == torch.float16:
+            with torch.autocast("cpu", enabled=False):
+                return real(input.float(), *args, **kwargs)
+        return real(input, *args, **kwargs)
+
+    F.interpolate = interpolate
+    try:
+        with torch.autocast("cpu", dtype=torch.float16):
+            yield
+    finally:
+        F.interpolate = real
+
+
+def autocast_kernels(name):
+    """(has an AutocastCPU kernel, has an AutocastCUDA kernel) for a dispatcher operator name such as `aten::mul.Tensor`."""
+    keys = {line.split(":", 1)[0] for line in torch._C._dispatch_dump(name).splitlines()}
+    return "AutocastCPU" in keys, "AutocastCUDA" in keys
+
+
+class OpRecorder(TorchDispatchMode):
+    """Names (with overload) of the aten operators that execute below it."""
+
+    def __init__(self):
+        super().__init__()
+        self.names = set()
+
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        s = func._schema
+        name = s.name + ("." + s.overload_name if s.overload_name else "")
+        self.names.add(name)
+        res = func(*args, **(kwargs or {}))
+        if name in INERT_OPS:     # inert only if no cast could have happened: every tensor in and out of one dtype
+            flat = [t for a in list(args) + [res] for t in (a if isinstance(a, (list, tuple)) else [a]) if isinstance(t, torch.Tensor)]
+            kinds = {t.dtype for t in flat}
+            if len(kinds) != 1 or INERT_OPS[name] not in (None, flat[0].dtype):
+                raise RuntimeError("%s met dtypes %s: its CPU / GPU autocast policies differ there" % (name, sorted(map(str, kinds))))
+        return res
+
+
+def autocast_policy(executed):
+    """The CPU / GPU autocast split of every operator the reference scenario executed plus the composite entry points.
+    Raises if an operator other than the emulated one (and the one OpRecorder proved inert) is cast on one device and not
+    on the other."""
+    ops = {}
+    for name in sorted(set(executed) | set(COMPOSITE_ENTRY_POINTS)):
+        cpu, cuda = autocast_kernels(name)
+        ops[name] = {"AutocastCPU": cpu, "AutocastCUDA": cuda}
+        if cpu != cuda and name not in EMULATED_OPS + tuple(INERT_OPS):
+            raise RuntimeError("autocast policy of %s differs between CPU (%s) and GPU (%s) and is not emulated: a fixture made "
+                               "on the CPU would not be what the reference computes on the GPU" % (name, cpu, cuda))
+    for name in EMULATED_OPS:
+        if name not in ops or ops[name] != {"AutocastCPU": False, "AutocastCUDA": True}:
+            raise RuntimeError("%s: the emulated divergence is no longer what this torch does (%s)" % (name, ops.get(name)))
+    return {"torch": torch.__version__, "emulated": list(EMULATED_OPS), "inert": sorted(INERT_OPS), "ops": ops}
+
+
+# the autocast fixture is stored in parts, so that no committed file exceeds 1 MiB; every key lives in exactly one part
+AUTOCAST_PARTS = ("heads", "pyramid", "offsets_a", "offsets_ab", "lookups")
+
+
+def autocast_part_of(key):
+    if key.startswith("out"):
+        return "lookups"
+    if key.startswith("A_pyr"):
+        return "pyramid"
+    if key.startswith("AB_offset"):
+        return "offsets_ab"
+    if "_offset" in key:
+        return "offsets_a"
+    return "heads"
+
+
+def corrblock_autocast_scenario(h, w, E_a, E_b, seed, inputs_of=None, executed=None):
+    """The life of corrblock_scenario run by the unchanged reference classes on the HALF maps inside cuda_autocast_on_cpu().
+    Same seed and draw order as corrblock_scenario: `inputs_of` (that scenario's fixture) must hold identical inputs, which
+    are not stored again.  `executed` (a set): receives the names of the aten operators that ran."""
+    global _gauss_calls
+    ref_corr, ref_ga = load_reference_glue()
+    g = torch.Generator().manual_seed(seed)
+    ofsMap, ofs_residual, GA = make_heads(ref_ga, h, w)
+    E = E_a + E_b
+    f1 = half_valued(g, (1, E, 128, h, w))
+    f2 = half_valued(g, (1, E, 128, h, w))
+    coords = [grid_coords(g, E, h, w, s) for s in (2.5, 4.0, 1.5)]
+    if inputs_of is not None:
+        for k, t in (("fmap1", f1), ("fmap2", f2), ("coords1", coords[0]), ("coords2", coords[1]), ("coords3", coords[2])):
+            assert inputs_of[k].dtype == t.numpy().dtype and np.array_equal(inputs_of[k], t.numpy()), "input %s differs" % k
+        assert (int(inputs_of["E_a"]), int(inputs_of["E_b"]), int(inputs_of["h"]), int(inputs_of["w"])) == (E_a, E_b, h, w)
+    tap = Tap(ofsMap=ofsMap, ofs_residual=ofs_residual, map=GA.map, meanMap=GA.meanMap, covMap=GA.covMap, GA=_Third(GA))
+    out, dtypes = {}, []
+
+    def put(key, t):
+        out[key] = n_(t)
+        dtypes.append("%s=%s" % (key, str(t.dtype).replace("torch.", "")))
+
+    def note(step, blk, result=None):     # dtype of every tensor the block holds at this step of its life
+        for l in range(4):
+            dtypes.append("%s:offset[%d]=%s" % (step, l, str(blk.offset[l].dtype).replace("torch.", "")))
+            dtypes.append("%s:corr_pyramid[%d]=%s" % (step, l, str(blk.corr_pyramid[l].dtype).replace("torch.", "")))
+        for nm in ("mean_n", "theta", "t"):
+            dtypes.append("%s:%s=%s" % (step, nm, str(getattr(blk, nm).dtype).replace("torch.", "")))
+        if result is not None:
+            dtypes.append("%s:out=%s" % (step, str(result.dtype).replace("torch.", "")))
+
+    def heads_of(tag):
+        put(tag + "_raw_o0", tap.pop("ofsMap")[0]), put(tag + "_raw_o1_low", tap.pop("ofs_residual")[0])
+        put(tag + "_raw_map", tap.pop("map")[0])
+        put(tag + "_raw_mean_ofs", tap.pop("meanMap")[0]), put(tag + "_raw_cov", tap.pop("covMap")[0])
+        put(tag + "_det", tap.pop("GA")[0])
+        (means, covs), = _gauss_calls
+        del _gauss_calls[:]
+        put(tag + "_means", means), put(tag + "_covs", covs)
+
+    rec = OpRecorder()
+    _gauss_calls = []
+    try:
+        with torch.no_grad(), rec, cuda_autocast_on_cpu():
+            fa1, fa2 = f1[:, :E_a].contiguous(), f2[:, :E_a].contiguous()
+            fb1, fb2 = f1[:, E_a:].contiguous(), f2[:, E_a:].contiguous()
+            A = ref_corr.CorrBlock(ofsMap, ofs_residual, GA, fa1, fa2, num_levels=4, radius=3)
+            heads_of("A")
+            note("A built", A)
+            put("A_mean_n", A.mean_n), put("A_theta", A.theta)
+            for l in range(4):
+                if l < 2:
+                    put("A_offset%d_init" % l, A.offset[l])
+                else:
+                    assert float(A.offset[l].abs().max()) == 0.0
+                put("A_pyr%d" % l, A.corr_pyramid[l])
+            r1, mean_n, theta = A(coords[0][:, :E_a])
+            assert mean_n is A.mean_n and theta is A.theta
+            note("A called", A, r1)
+            put("out1", r1), put("A_offset0_after1", A.offset[0]), put("A_offset1_after1", A.offset[1])
+
+            B = ref_corr.CorrBlock(ofsMap, ofs_residual, GA, fb1, fb2, num_levels=4, radius=3)
+            heads_of("B")
+            note("B built", B)
+            put("B_mean_n", B.mean_n), put("B_theta", B.theta)
+            for l in range(2):
+                put("B_offset%d_init" % l, B.offset[l])
+            A = A.cat(B)
+            note("A.cat(B)", A)
+            r2, _, _ = A(coords[1])
+            note("AB called", A, r2)
+            put("out2", r2), put("AB_offset0_after2", A.offset[0]), put("AB_offset1_after2", A.offset[1])
+
+            keep = torch.ones(E, dtype=torch.bool)
+            keep[E // 2] = False
+            A = A[keep]
+            note("AB[keep]", A)
+            r3, _, _ = A(coords[2][:, keep])
+            note("AB[keep] called", A, r3)
+            put("out3", r3), put("AB_offset1_after3", A.offset[1])
+            assert float(A.offset[2].abs().max()) == 0.0 and A.offset[2].shape[0] == E - 1
+
+            # the raw all-pairs product (corr.py:145-152), from a call of its own on the same inputs
+            put("A_raw_product", ref_corr.CorrBlock.corr(fa1, fa2)), put("B_raw_product", ref_corr.CorrBlock.corr(fb1, fb2))
+    finally:
+        _gauss_calls = None
+        tap.close()
+    if executed is not None:
+        executed.update(rec.names)
+    out["keep"] = keep.numpy()
+    out["dtypes"] = np.array(dtypes)
+    return out
+
+
+class _Third:
+    """Lets Tap keep the third output (det) of GaussianMask.forward."""
+
+    def __init__(self, mod):
+        self.mod = mod
+
+    def register_forward_hook(self, fn):
+        return self.mod.register_forward_hook(lambda m, i, o: fn(m, i, o[2]))
+
+
 def altcorr_scenario(h, w, N, edges_calls, seed, store_float_run=True, store_raw=True):
     """AltCorrBlock as update_lowmem drives it (factor_graph.py:262-279): one block over the frame buffer, one call per
     chunk of edges.  Run twice by the reference: on the half buffer (what depth_video holds) and on its float copy."""
@@ -376,6 +594,15 @@ def main(outdir):
     save("glue_altcorr_16x16", altcorr_scenario(16, 16, 4, [[(0, 1), (0, 2), (1, 0), (1, 1)], [(2, 3), (3, 0)]], seed=103))
     save("glue_altcorr_24x32", altcorr_scenario(24, 32, 3, [[(1, 2), (0, 1), (2, 0)]], seed=104, store_float_run=False,
                                                    store_raw=False))
+    executed = set()
+    auto = corrblock_autocast_scenario(16, 16, 2, 1, seed=101, executed=executed,
+                                       inputs_of=np.load(os.path.join(outdir, "glue_corrblock_16x16.npz"), allow_pickle=False))
+    for part in AUTOCAST_PARTS:
+        save("glue_corrblock_autocast_16x16_" + part, {k: v for k, v in auto.items() if autocast_part_of(k) == part})
+    with open(os.path.join(outdir, "glue_autocast_policy.json"), "w") as fh:
+        json.dump(autocast_policy(executed), fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote glue_autocast_policy.json")
     print("GLUE_GOLDEN_DONE")
 
 
