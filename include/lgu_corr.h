@@ -1008,6 +1008,53 @@ typedef struct {
 } lgu_conv1_args;
 int lgu_conv1x1_o128_h16(lgu_conv1_args args, void* stream);
 
+/* ---- the encoders' residual stages: Conv2d(Cin, Cout, 3, stride=s, padding=1) + bias with the norm-free tail of a
+ * ResidualBlock as its epilogue and, with stride 2, the block's Conv2d(Cin, Cout, 1, stride=2) downsample branch in the same
+ * launch, under float16 autocast (csrc/encconv.hip).  Reference droid_slam/modules/extractor.py: layer1..3 of BasicEncoder.
+ * (Cin, Cout, s) is one of (32,32,1), (32,64,2), (64,64,1), (64,128,2), (128,128,1); anything else: LGU_E_UNSUPPORTED.
+ * x (N,Cin,H,W) NCHW contiguous IEEE half; out, res and r (N,Cout,Ho,Wo) NCHW contiguous IEEE half with Ho = ceil(H / s),
+ * Wo = ceil(W / s) (PyTorch's rule for k = 3, p = 1); out and r are fully written and nothing outside them, and overlap neither
+ * x nor res nor one another.  Rounding points:
+ *   w_h = half(weight), b_h = half(bias)                    round to nearest even, in the pack; x is half and used as it is
+ *   s   = b_h + sum over ky, kx, c of x[c][s y+ky-1][s x+kx-1] * w_h[co][c][ky][kx]
+ *                                                           exact half x half products, fp32 accumulation, zero padding:
+ *                                                           a row or column outside the image, row H and column W of an
+ *                                                           odd size included, contributes exact zeros
+ *   y0  = half(s)                                           ONE rounding
+ *   y   = y0                                                flags 0 (what an instance norm of the feature encoder reads)
+ *       = y0 < 0 ? 0 : y0                                   LGU_ENCCONV_RELU: a compare and select, NaN is kept
+ *       = relu(half(res + relu(y0)))                        LGU_ENCCONV_RESIDUAL: the add of two halves in fp32, ONE rounding,
+ *                                                           PyTorch's bits of relu(x + relu(conv)) on half tensors
+ *   r   = half(b'_h + sum over c of x[c][2 y][2 x] * w'_h[co][c])    the downsample branch (dpack, dbias, r all given; s = 2
+ *                                                           only): the centre tap of the staged window, accumulators of its
+ *                                                           own from b'_h over the channel blocks in ascending order, the
+ *                                                           identity epilogue always; r does not depend on wpack or flags
+ * The accumulator starts at b_h and takes its 9 Cin / 32 K steps in a fixed order, tap-major (ky, kx), then blocks of 32
+ * channels, whatever the tile and the split of the output channels over workgroups: the bits of an image depend on that
+ * image, H and W only, not on N or on its position in the batch, and out has the same bits with or without the branch.  A
+ * NaN or infinite x reaches exactly the outputs whose window holds it, and its one pixel of r where its row and column are
+ * even; a NaN of res reaches one element.  No atomics, no workspace, no host synchronisation.
+ * wpack: 9 * Cin * Cout halves laid out [9 taps t = 3 ky + kx][Cin/32 channel blocks kc][Cout/16 channel tiles ct][64 lanes l]
+ *   [8 halves j], the B operand of v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is
+ *   w_h[16 ct + (l & 15)][32 kc + 8 (l >> 4) + j][t / 3][t % 3].  dpack: Cin * Cout halves [Cin/32 kc][Cout/16 ct][64 l][8 j],
+ *   element j of lane l is w'_h[16 ct + (l & 15)][32 kc + 8 (l >> 4) + j].  Every slot of either holds a weight.  16-byte
+ *   aligned, otherwise LGU_E_UNSUPPORTED.  bias, dbias: Cout halves.
+ * x, res, bias, dbias, out and r are served at the alignment of their element with the same bits: res is loaded and out and
+ *   r are stored 16 bytes at a time where Wo % 8 == 0 and the pointer is 16-byte aligned, by element otherwise.
+ * Every N >= 0, H >= 1, W >= 1 is served; N == 0: LGU_OK, nothing launched.  N < 0, H < 1, W < 1, an unknown flag, both flags,
+ * a null x, wpack, bias or out, res without LGU_ENCCONV_RESIDUAL or the flag without res, an incomplete (dpack, dbias, r), the
+ * branch with s != 2, or an operand below its element's alignment: LGU_E_BADARG; another (Cin, Cout, s), a pack that is not
+ * 16-byte aligned or more than INT_MAX workgroups (at most N * ceil(Wo / 32) * ceil(Ho / 2) * Cout / 32): LGU_E_UNSUPPORTED.  Every refusal comes before any launch and writes
+ * nothing.  The operands travel in one parameter block passed by value. */
+#define LGU_ENCCONV_RELU 1       /* flags: y = relu(y0) */
+#define LGU_ENCCONV_RESIDUAL 2   /* flags: y = relu(half(res + relu(y0))) */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; const void* res; void* out;   /* bias: Cout halves */
+  const void* dpack; const void* dbias; void* r;                                    /* all three, or all null */
+  int N, H, W, Cin, Cout, stride, flags;
+} lgu_encconv_args;
+int lgu_encconv3x3_h16(lgu_encconv_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,11 +10,13 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, conv1, conv3, encoder, features, flow, geom, graph, gru, heads, lie, ops, sharded, upmask  # noqa: F401
+from . import _build, _lib, aggregate, ba, context, conv1, conv3, encconv, encoder, features, flow, geom, graph, gru, heads, lie, ops, sharded, upmask  # noqa: F401
 from . import update  # noqa: F401
 from .conv1 import Conv1  # noqa: F401
 from .conv3 import Conv3, Conv3Stack, conv3x3_fanout  # noqa: F401
+from .context import ContextEncoder  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
+from .encconv import enc_conv3x3, pack_enc1, pack_enc3  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
 from .flow import FlowEncoder  # noqa: F401

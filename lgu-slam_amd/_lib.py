@@ -67,6 +67,12 @@ class GruConvArgs(ctypes.Structure):
                 ("Cout", _int), ("mode", _int), ("flags", _int)]
 
 
+class EncConvArgs(ctypes.Structure):
+    """lgu_encconv_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("res", _vp), ("out", _vp), ("dpack", _vp), ("dbias", _vp), ("r", _vp),
+                ("N", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int), ("flags", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -196,6 +202,9 @@ SIGNATURES = {
     "lgu_upmask_upsample_f32": [UpmaskUpsArgs, _vp],
     # 1x1 convolution, Cin <= 224 -> 128 (corr_encoder[0]): {x, wpack, bias, out, N, Cin, H, W, flags} by value, stream
     "lgu_conv1x1_o128_h16": [Conv1Args, _vp],
+    # the encoders' residual-stage 3x3 convolutions with their tail and the 1x1 stride-2 branch: {x, wpack, bias, res, out,
+    # dpack, dbias, r, N, H, W, Cin, Cout, stride, flags} by value, stream
+    "lgu_encconv3x3_h16": [EncConvArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],

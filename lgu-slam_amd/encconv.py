@@ -1,0 +1,163 @@
+"""The 3x3 convolutions of the encoders' residual stages (reference droid_slam/modules/extractor.py: layer1..3 of
+BasicEncoder, two ResidualBlocks each, DIM = 32):
+
+    layer1  Conv2d(32, 32, 3, padding=1) x 4
+    layer2  Conv2d(32, 64, 3, stride=2, padding=1) + Conv2d(32, 64, 1, stride=2),  Conv2d(64, 64, 3, padding=1) x 3
+    layer3  Conv2d(64, 128, 3, stride=2, padding=1) + Conv2d(64, 128, 1, stride=2), Conv2d(128, 128, 3, padding=1) x 3
+
+Under float16 autocast each of them is the library's convolution with its layout passes and a bias launch, and in the
+norm-free context encoder a ReLU, an add and another ReLU behind it.  `enc_conv3x3` (csrc/encconv.hip) evaluates the
+convolution, the bias and that tail in one launch on the matrix cores, NCHW half in and NCHW half out, and on the strided
+shapes gives the block's 1x1 stride-2 downsample branch from the same launch (include/lgu_corr.h states the rounding
+points).  `context.ContextEncoder` and `features.FeatureEncoder(convs=True)` are its callers.
+
+`enc_conv3x3`: contiguous HIP device tensors only (no CPU fallback), every argument error raised before anything is
+launched, no host synchronisation (graph-capturable), forward only: an input that requires grad is refused while grad mode
+is on.  There is no fp32 kernel: fp32 evaluation is the module's own forward.
+"""
+import torch
+
+from . import _lib
+from ._host import check_dtype, check_layer_operands, check_shape, is_conv, launch
+from ._host import stream as _stream
+
+# (Cin, Cout, stride) of Conv2d(Cin, Cout, 3, stride, padding=1) the kernel serves
+SHAPES = ((32, 32, 1), (32, 64, 2), (64, 64, 1), (64, 128, 2), (128, 128, 1))
+_CHANNELS = tuple(sorted({(cin, cout) for cin, cout, _ in SHAPES}))
+_STRIDE_OF = {(cin, cout): s for cin, cout, s in SHAPES}
+RELU, RESIDUAL = 1, 2            # include/lgu_corr.h LGU_ENCCONV_RELU, LGU_ENCCONV_RESIDUAL
+
+# Per (Cin, Cout, stride), the number of output pixels N * Ho * Wo below which the measured fused layer does not beat the
+# module's own call with the tail it replaces beyond the two spreads (tools/prof_encconv.py):
+# ContextEncoder and FeatureEncoder(convs=True) send such calls to the module's convolution.  0: every measured class (1
+# and 16 frames of 384x512) kept the fused path.
+MIN_FUSED_PIXELS = {shape: 0 for shape in SHAPES}
+
+
+def _check_channels(weight, k, who):
+    ok = weight.dim() == 4 and (weight.shape[1], weight.shape[0]) in _CHANNELS and (k == 3 or weight.shape[0] != weight.shape[1])
+    cin, cout = (weight.shape[1], weight.shape[0]) if ok else (64, 128)
+    if not ok or tuple(weight.shape[2:]) != (k, k):
+        raise RuntimeError("%s: weight must be (Cout,Cin,%d,%d) with (Cin, Cout) in %s, got %s"
+                           % (who, k, k, [c for c in _CHANNELS if k == 3 or c[0] != c[1]], tuple(weight.shape)))
+    return cin, cout
+
+
+def pack_enc3(weight, bias):
+    """(wpack (9,Cin/32,Cout/16,64,8) half, bias_h (Cout) half) of a Conv2d(Cin, Cout, 3) weight (Cout,Cin,3,3) and bias
+    (Cout), (Cin, Cout) one of (32,32), (32,64), (64,64), (64,128), (128,128), on the weight's device.
+    wpack[t, kc, ct, l, j] = half(weight)[16 ct + (l & 15), 32 kc + 8 (l >> 4) + j, t // 3, t % 3]: the B operand of
+    v_mfma_f32_16x16x32_f16, one tap t = 3 ky + kx and one block kc of 32 input channels per K step, channel tile ct of 16
+    output channels, lane l, element j.  Every slot holds a weight."""
+    cin, cout = _check_channels(weight, 3, "pack_enc3")
+    check_shape([(bias, "bias")], (cout,))
+    with torch.no_grad():
+        wh = weight.detach().to(torch.float16)
+        # [ct][cl][kc][g][j][t] -> [t][kc][ct][g][cl][j]: lane l = 16 g + cl
+        wpack = wh.reshape(cout // 16, 16, cin // 32, 4, 8, 9).permute(5, 2, 0, 3, 1, 4).reshape(9, cin // 32, cout // 16, 64, 8)
+        bias_h = bias.detach().to(device=wh.device, dtype=torch.float16).contiguous()
+    return wpack.contiguous(), bias_h
+
+
+def pack_enc1(weight, bias):
+    """(dpack (Cin/32,Cout/16,64,8) half, bias_h (Cout) half) of a downsample branch's Conv2d(Cin, Cout, 1, stride=2)
+    weight (Cout,Cin,1,1) and bias (Cout), (Cin, Cout) (32,64) or (64,128), on the weight's device.
+    dpack[kc, ct, l, j] = half(weight)[16 ct + (l & 15), 32 kc + 8 (l >> 4) + j, 0, 0]: block kc of 32 input channels,
+    channel tile ct of 16 output channels, lane l, element j.  Every slot holds a weight."""
+    cin, cout = _check_channels(weight, 1, "pack_enc1")
+    check_shape([(bias, "bias")], (cout,))
+    with torch.no_grad():
+        wh = weight.detach().to(torch.float16)
+        # [ct][cl][kc][g][j] -> [kc][ct][g][cl][j]
+        dpack = wh.reshape(cout // 16, 16, cin // 32, 4, 8).permute(2, 0, 3, 1, 4).reshape(cin // 32, cout // 16, 64, 8)
+        bias_h = bias.detach().to(device=wh.device, dtype=torch.float16).contiguous()
+    return dpack.contiguous(), bias_h
+
+
+def out_size(H, W, stride):
+    """(Ho, Wo) = (ceil(H / stride), ceil(W / stride)): torch's rule for kernel 3, padding 1."""
+    return (H + stride - 1) // stride, (W + stride - 1) // stride
+
+
+def enc_conv3x3(x, pack, stride=1, relu=False, residual=None, down=None):
+    """The convolution Conv2d(Cin, Cout, 3, stride, padding=1) of half x (N,Cin,H,W) with `pack` = (wpack, bias_h) of
+    `pack_enc3` (the bias gives Cout), as a new (N,Cout,Ho,Wo) half tensor y, (Ho, Wo) = out_size(H, W, stride):
+
+        y0 = half(b_h + sum x * w_h)      exact products, fp32 accumulation from the bias in a fixed order, one rounding
+        y  = y0                           relu=False, residual=None
+           = relu(y0)                     relu=True
+           = relu(residual + relu(y0))    residual (N,Cout,Ho,Wo) half: the tail of a norm-free ResidualBlock, the add
+                                          rounded to half once; relu=True says nothing more with it
+
+    down = (dpack, dbias_h) of `pack_enc1` (stride 2 only): returns (y, r) with r = half(b'_h + sum_c x[c, 2y, 2x] w'_h),
+    the block's 1x1 stride-2 downsample branch, from the same launch; y has the bits of the call without it.  NaN is kept.
+
+    Refusals, in this order, all before anything is launched: x not 4-D, stride not 1 or 2, pack not a pair, bias_h not 1-D,
+    (Cin, Cout, stride) not a served shape (UnsupportedShape), the size of wpack, x not half, the shape then the dtype of
+    residual, down with stride 1, down not a pair, the sizes of dpack and dbias_h, then contiguity, dtypes (half), grad
+    and device of x, wpack, bias_h, residual, dpack, dbias_h in that order (_host.check_layer_operands); then N == 0
+    returns the empty result and H*W == 0 raises.  x, residual and the biases are served at element alignment; a pack that
+    is not 16-byte aligned (never the case for what the pack functions return) raises UnsupportedShape."""
+    if x.dim() != 4:
+        raise RuntimeError("x must be (N,Cin,H,W), got %s" % (tuple(x.shape),))
+    if stride not in (1, 2):
+        raise RuntimeError("stride must be 1 or 2, got %r" % (stride,))
+    if not isinstance(pack, (tuple, list)) or len(pack) != 2:
+        raise RuntimeError("pack must be (wpack, bias_h) of pack_enc3")
+    wpack, bias_h = pack
+    if bias_h.dim() != 1:
+        raise RuntimeError("bias_h must be (Cout,), got %s" % (tuple(bias_h.shape),))
+    N, cin, H, W = x.shape
+    cout = bias_h.shape[0]
+    if (cin, cout, stride) not in SHAPES:
+        raise _lib.UnsupportedShape("enc_conv3x3 serves (Cin, Cout, stride) in %s, got (%d, %d, %d)" % (list(SHAPES), cin, cout, stride))
+    if wpack.numel() != 9 * cin * cout:
+        raise RuntimeError("wpack must hold %d halves (pack_enc3, %d -> %d), got %s" % (9 * cin * cout, cin, cout, tuple(wpack.shape)))
+    check_dtype([(x, "x")], torch.float16)
+    Ho, Wo = out_size(H, W, stride)
+    named = [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")]
+    if residual is not None:
+        check_shape([(residual, "residual")], (N, cout, Ho, Wo))
+        check_dtype([(residual, "residual")], torch.float16)
+        named.append((residual, "residual"))
+    if down is not None:
+        if stride != 2:
+            raise RuntimeError("down (the 1x1 stride-2 branch) needs stride=2")
+        if not isinstance(down, (tuple, list)) or len(down) != 2:
+            raise RuntimeError("down must be (dpack, dbias_h) of pack_enc1")
+        dpack, dbias_h = down
+        if dpack.numel() != cin * cout:
+            raise RuntimeError("dpack must hold %d halves (pack_enc1, %d -> %d), got %s" % (cin * cout, cin, cout, tuple(dpack.shape)))
+        check_shape([(dbias_h, "dbias_h")], (cout,))
+        named += [(dpack, "dpack"), (dbias_h, "dbias_h")]
+    check_layer_operands("enc_conv3x3", named)
+    out = torch.empty((N, cout, Ho, Wo), dtype=torch.float16, device=x.device)
+    r = torch.empty_like(out) if down is not None else None
+    if N > 0:
+        if H * W == 0:
+            raise RuntimeError("enc_conv3x3: empty frame (H*W = 0)")
+        flags = RESIDUAL if residual is not None else (RELU if relu else 0)
+        args = _lib.EncConvArgs(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                out.data_ptr(), down[0].data_ptr() if down is not None else None,
+                                down[1].data_ptr() if down is not None else None, r.data_ptr() if down is not None else None,
+                                N, H, W, cin, cout, stride, flags)
+        launch("lgu_encconv3x3_h16", "enc_conv3x3", x.device, args, _stream(x))
+    return out if down is None else (out, r)
+
+
+def shape_of(conv):
+    """(Cin, Cout, stride) if `conv` is a Conv2d(Cin, Cout, 3, stride, padding=1) with a bias the kernel serves, else None."""
+    for shape in SHAPES:
+        if is_conv(conv, shape[0], shape[1], 3, stride=shape[2], pad=1, bias=True):
+            return shape
+    return None
+
+
+def serves(conv, x):
+    """A call of the eligible `conv` on the half NCHW tensor x is large enough for the fused path (MIN_FUSED_PIXELS, read
+    at the call)."""
+    shape = shape_of(conv)
+    if shape is None or x.dim() != 4 or x.shape[1] != shape[0] or x.shape[2] * x.shape[3] == 0:
+        return False
+    Ho, Wo = out_size(x.shape[2], x.shape[3], shape[2])
+    return x.shape[0] * Ho * Wo >= MIN_FUSED_PIXELS[shape]

@@ -2,7 +2,10 @@
 norm_fn='instance'), run on every incoming frame by MotionFilter.track and PoseTrajectoryFiller) on the HIP kernels of
 csrc/instnorm.hip.
 
-The 13 convolutions stay the module's own calls (MIOpen).  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
+By default the 13 convolutions stay the module's own calls (MIOpen); with `convs=True` the twelve 3x3 convolutions of
+layer1..3 go through csrc/encconv.hip under float16 autocast (`encconv.enc_conv3x3`, identity epilogue, the 1x1 downsample
+branch of a strided block from its first launch), opt-in because the library's summation order differs and
+`features.install(m)` keeps its bits.  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
 6 residual add + ReLU pairs, becomes one call per site group, 13 per forward: each convolution output is read once, the
 statistics are taken in fp32 from the stored values, and the block output is rounded to the tensor type once.  A call
 is one launch while H*W <= resident_limit(dtype): every site of a 384x512 frame under float16 autocast (13 launches).
@@ -22,8 +25,8 @@ import ctypes
 
 import torch
 
-from . import _lib
-from ._host import (FLOAT_OR_HALF, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, dtype_name,
+from . import _lib, encconv
+from ._host import (FLOAT_OR_HALF, PackCache, bind, check_contiguous, check_device, check_dtype, check_no_grad, check_shape, dtype_name,
                     fused_dtype, is_conv, launch, typed, unbind)
 from ._host import ptr as _ptr, stream as _stream
 
@@ -141,10 +144,15 @@ class FeatureEncoder:
     else goes to the module's own forward unchanged: CPU tensors, a bfloat16 autocast, channels-last, training with
     gradients, a dropout in training mode.
 
+    convs=True: under float16 autocast the twelve residual-stage convolutions are `encconv.enc_conv3x3` launches (identity
+    epilogue; a strided block's 1x1 downsample branch comes from its first launch) where the call has at least
+    encconv.MIN_FUSED_PIXELS of its shape and the layer has one of the kernel's shapes; the instance-norm calls are the
+    same.  The fp32 path does not change.  The default, False, keeps every convolution the module's own.
+
     Construction refuses (RuntimeError naming the attribute) anything but conv1 / norm1 / layer1..3 of two residual
     blocks each / conv2 with InstanceNorm2d(affine=False, track_running_stats=False) at every norm site."""
 
-    def __init__(self, module):
+    def __init__(self, module, convs=False):
         conv1 = getattr(module, "conv1", None)
         if not isinstance(conv1, torch.nn.Conv2d):
             raise RuntimeError("FeatureEncoder: conv1 must be a Conv2d")
@@ -186,6 +194,8 @@ class FeatureEncoder:
             raise RuntimeError("FeatureEncoder: conv2 must be a Conv2d")
         _check_conv(conv2, cin, conv2.out_channels, 1, 1, 0, "conv2")
         self.module = module
+        self.convs = bool(convs)
+        self._packs = PackCache()
         self.fused_calls = 0
 
     def _convs(self):
@@ -223,17 +233,31 @@ class FeatureEncoder:
         if not ok(y):
             return None
         y = _instnorm(y, None, y, 0, m.norm1.eps)
+        own = self.convs and dt == torch.float16      # the residual stages on csrc/encconv.hip
         for blk in self.blocks:
-            t = blk.conv1(y)
+            r = None
+            if own and encconv.serves(blk.conv1, y):
+                p1 = self._packs.of(blk.conv1, encconv.pack_enc3)
+                if blk.downsample is None:
+                    t = encconv.enc_conv3x3(y, p1)
+                else:
+                    t, r = encconv.enc_conv3x3(y, p1, stride=2, down=self._packs.of(blk.downsample[0], encconv.pack_enc1))
+            else:
+                t = blk.conv1(y)
             if not ok(t):
                 return None
-            t = blk.conv2(_instnorm(t, None, t, 0, blk.norm1.eps))
+            t = _instnorm(t, None, t, 0, blk.norm1.eps)
+            if own and encconv.serves(blk.conv2, t):
+                t = encconv.enc_conv3x3(t, self._packs.of(blk.conv2, encconv.pack_enc3))
+            else:
+                t = blk.conv2(t)
             if not ok(t):
                 return None
             if blk.downsample is None:
                 y = _instnorm(t, y, t, 1, blk.norm2.eps)
             else:
-                r = blk.downsample[0](y)
+                if r is None:
+                    r = blk.downsample[0](y)
                 if not ok(r):
                     return None
                 y = _instnorm(t, r, t, 2, blk.norm2.eps)
@@ -252,11 +276,11 @@ class FeatureEncoder:
         return out
 
 
-def install(module):
+def install(module, convs=False):
     """Bind a FeatureEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
-    unchanged), so every caller of the encoder reaches the fused path.  Returns the wrapper; a second call returns the
-    one already installed."""
-    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module))
+    unchanged), so every caller of the encoder reaches the fused path.  `convs` as in FeatureEncoder.  Returns the
+    wrapper; a second call returns the one already installed (with the `convs` it was made with)."""
+    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module, convs=convs))
 
 
 def uninstall(module):

@@ -1,0 +1,185 @@
+#!/usr/bin/env python3
+"""Device-event medians of the fused residual-stage convolutions of the encoders (lgu_slam_amd.encconv, csrc/encconv.hip)
+against the module's own autocast calls, with the same seeded weights on the same GPU, at 1 and 16 frames of 384x512
+(MotionFilter.track and PoseTrajectoryFiller).  Writes profiles/encconv_prof.json and prints it as ONE JSON line.
+
+Forms, per workload:
+  <Cin>-<Cout>-s<stride>/bare       enc_conv3x3(x)                      against conv(x)
+  <Cin>-<Cout>-s<stride>/relu       enc_conv3x3(x, relu=True)           against relu_(conv(x))
+  <Cin>-<Cout>-s1/residual          enc_conv3x3(x, residual=r)          against relu_(r + relu_(conv(x)))
+  <Cin>-<Cout>-s2/down              enc_conv3x3(x, relu=True, down=..)  against enc_conv3x3(x, relu=True) + the module's 1x1
+  cnet                              context.install(cnet)               against the module's own forward
+  fnet_convs                        features.install(fnet, convs=True)  against features.install(fnet)
+Each layer form runs at the plane its layer sees in a 384x512 frame (32 channels: 192x256, 64: 96x128, 128: 48x64).
+Method (tools/prof_conv3.py's): every timed call runs on the next of ROT disjoint input sets, the two sides alternate call
+by call in one process, and a spin kernel ahead of the first event keeps the host's enqueue time out of the window.
+Reported per side: median, quartiles and spread = p75 - p25 (ms).  `keep_fused`: fused median + spread < other median -
+spread.  `min_fused_pixels`: per shape, the smallest number of output pixels N*Ho*Wo from which every measured class of
+every layer form of the shape keeps the fused path, the rule by which lgu_slam_amd.encconv.MIN_FUSED_PIXELS is set (0:
+every class keeps it).
+Usage: prof_encconv.py [--reps N] [--out PATH] [--forms a,b] [--frames 1,16]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import lgu_slam_amd  # noqa: E402
+from tests import context_restatement as RC  # noqa: E402
+from tests import features_restatement as RF  # noqa: E402
+
+ROT = 8
+SPIN = 400000
+FRAME = (384, 512)
+PLANE = {32: (192, 256), 64: (96, 128), 128: (48, 64)}
+OUT = os.path.join(ROOT, "profiles", "encconv_prof.json")
+E = lgu_slam_amd.encconv
+
+
+def sid(shape):
+    return "%d-%d-s%d" % shape
+
+
+def layer_forms():
+    forms = []
+    for shape in E.SHAPES:
+        forms += [sid(shape) + "/bare", sid(shape) + "/relu", sid(shape) + ("/residual" if shape[2] == 1 else "/down")]
+    return forms
+
+
+FORMS = layer_forms() + ["cnet", "fnet_convs"]
+
+
+def stats(ts):
+    q = np.percentile(ts, [25, 50, 75])
+    return {"median_ms": float(q[1]), "p25_ms": float(q[0]), "p75_ms": float(q[2]), "spread_ms": float(q[2] - q[0]),
+            "min_ms": float(np.min(ts))}
+
+
+def block_of(cnet, shape):
+    cin, cout, st = shape
+    layer = {32: cnet.layer1, 64: cnet.layer2, 128: cnet.layer3}[cout]
+    return layer[0] if cin != cout else layer[1]
+
+
+def sides_of(form, cnet, fnet, fnet_twin, frames):
+    """(fused, other, inputs): two callables of one input and ROT inputs."""
+    if form == "cnet":
+        xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
+        own = type(cnet).forward
+        return lgu_slam_amd.context.ContextEncoder(cnet), (lambda x: own(cnet, x)), xs
+    if form == "fnet_convs":
+        xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
+        return lgu_slam_amd.features.FeatureEncoder(fnet_twin, convs=True), lgu_slam_amd.features.FeatureEncoder(fnet), xs
+    name, tail = form.split("/")
+    shape = [s for s in E.SHAPES if sid(s) == name][0]
+    cin, cout, st = shape
+    blk = block_of(cnet, shape)
+    conv = blk.conv1 if st == 2 else blk.conv2
+    pack = E.pack_enc3(conv.weight, conv.bias)
+    H, W = PLANE[cin]
+    g = torch.Generator().manual_seed(7 + cin)
+    xs = []
+    for _ in range(ROT):
+        x = torch.randn((frames, cin, H, W), generator=g) * 2.0
+        xs.append(x.clamp_(min=0.0).half().cuda())          # behind a ReLU: exact zeros
+    if tail == "bare":
+        return (lambda x: E.enc_conv3x3(x, pack, stride=st)), conv, xs
+    if tail == "relu":
+        return (lambda x: E.enc_conv3x3(x, pack, stride=st, relu=True)), (lambda x: torch.relu_(conv(x))), xs
+    if tail == "residual":
+        res = (torch.randn((frames, cout) + E.out_size(H, W, st), generator=g) * 2.0).clamp_(min=0.0).half().cuda()
+        return (lambda x: E.enc_conv3x3(x, pack, residual=res)), (lambda x: torch.relu_(res + torch.relu_(conv(x)))), xs
+    down = blk.downsample[0]
+    dpack = E.pack_enc1(down.weight, down.bias)
+    return ((lambda x: E.enc_conv3x3(x, pack, stride=2, relu=True, down=dpack)),
+            (lambda x: (E.enc_conv3x3(x, pack, stride=2, relu=True), down(x))), xs)
+
+
+def timed(fns, xs, reps, warmup=3):
+    """{side: [ms]}: the sides alternate call by call; call k of a side uses input set k % ROT."""
+    ts = {k: [] for k in fns}
+    for k in range(warmup + reps):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda._sleep(SPIN)
+            a.record()
+            fn(xs[k % ROT])
+            b.record()
+            b.synchronize()
+            if k >= warmup:
+                ts[name].append(a.elapsed_time(b))
+    return ts
+
+
+def measure(reps, forms, frames_list):
+    res = {}
+    cnet = RC.make_case("context_cnet_2x40x56")[0].cuda()
+    fnet, fnet_twin = RF.make_case("features_fnet_2x40x56")[0].cuda(), RF.make_case("features_fnet_2x40x56")[0].cuda()
+    for frames in frames_list:
+        r = {"frames": frames, "H": FRAME[0], "W": FRAME[1], "forms": {}}
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+            for form in forms:
+                fused, other, xs = sides_of(form, cnet, fnet, fnet_twin, frames)
+                ts = timed({"fused": fused, "other": other}, xs, reps)
+                del xs
+                torch.cuda.empty_cache()
+                f, o = stats(ts["fused"]), stats(ts["other"])
+                d = {"fused": f, "other": o, "speedup": o["median_ms"] / f["median_ms"],
+                     "keep_fused": bool(f["median_ms"] + f["spread_ms"] < o["median_ms"] - o["spread_ms"])}
+                if "/" in form:
+                    shape = [s for s in E.SHAPES if sid(s) == form.split("/")[0]][0]
+                    ho, wo = E.out_size(*PLANE[shape[0]], shape[2])
+                    d["out_pixels"] = frames * ho * wo
+                r["forms"][form] = d
+        res["frames_%d" % frames] = r
+    return res
+
+
+def thresholds(workloads):
+    """Per shape: 0 if every class of every layer form keeps the fused path, else the pixel count of the smallest class
+    from which all larger ones keep it (1 << 62: none does)."""
+    out = {}
+    for shape in E.SHAPES:
+        per = {}
+        for w in workloads.values():
+            for form, d in w["forms"].items():
+                if form.startswith(sid(shape) + "/"):
+                    per[d["out_pixels"]] = per.get(d["out_pixels"], True) and d["keep_fused"]
+        classes = sorted(per.items())
+        need = 0
+        for i, (pixels, keep) in enumerate(classes):
+            if not keep:
+                need = classes[i + 1][0] if i + 1 < len(classes) else 1 << 62
+        out[sid(shape)] = need
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--forms", help="comma-separated subset of the forms to time (e.g. a variant library under LGU_LIB_PATH); "
+                    "no thresholds are derived from a subset")
+    ap.add_argument("--frames", default="1,16")
+    args = ap.parse_args()
+    lgu_slam_amd._lib.load()
+    E.MIN_FUSED_PIXELS = {s: 0 for s in E.SHAPES}      # measure the fused path at every class; the rule is applied afterwards
+    forms = args.forms.split(",") if args.forms else list(FORMS)
+    workloads = measure(args.reps, forms, [int(f) for f in args.frames.split(",")])
+    doc = {"tool": "prof_encconv", "device": torch.cuda.get_device_name(0), "lib": lgu_slam_amd._lib.version(),
+           "reps": args.reps, "rotation": ROT, "workloads": workloads}
+    if not args.forms:
+        doc["min_fused_pixels"] = thresholds(workloads)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
+    print(json.dumps(doc, sort_keys=True))
+
+
+if __name__ == "__main__":
+    main()
