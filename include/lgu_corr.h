@@ -1055,6 +1055,76 @@ typedef struct {
 } lgu_encconv_args;
 int lgu_encconv3x3_h16(lgu_encconv_args args, void* stream);
 
+/* ---- the encoders' stem: Conv2d(3, 32, 7, stride=2, padding=3) + bias with an optional ReLU, one launch, under float16
+ * autocast (csrc/encends.hip).  Reference droid_slam/modules/extractor.py: conv1 of BasicEncoder (+ relu1 without a norm).
+ * x (N,3,H,W) NCHW contiguous float32, or IEEE half with LGU_ENCSTEM_X_HALF; out (N,32,Ho,Wo) NCHW contiguous IEEE half with
+ * Ho = ceil(H / 2), Wo = ceil(W / 2) (PyTorch's rule for k = 7, s = 2, p = 3), fully written and nothing outside it; it does
+ * not overlap x.  Rounding points:
+ *   x_h = half(x)                                           round to nearest even, in the kernel; a half x is used as it is
+ *   w_h = half(weight), b_h = half(bias)                    in the pack
+ *   s   = b_h + sum over ky, kx, c of x_h[c][2 y+ky-3][2 x+kx-3] * w_h[co][c][ky][kx]
+ *                                                           exact half x half products, fp32 accumulation that starts at b_h
+ *                                                           and takes the seven window rows in ascending ky; zero padding: a
+ *                                                           row or column outside the image, the one just past an odd size
+ *                                                           included, contributes exact zeros
+ *   y0  = half(s)                                           ONE rounding
+ *   y   = y0                                                flags without LGU_ENCSTEM_RELU (what an instance norm reads)
+ *       = y0 < 0 ? 0 : y0                                   LGU_ENCSTEM_RELU: a compare and select, NaN is kept
+ * The bits of an image depend on that image, H and W only, not on N, its position in the batch or the launch geometry.  A
+ * NaN or infinite x reaches exactly the outputs whose 7x7 window holds it.  No atomics, no workspace, no host
+ * synchronisation.
+ * wpack: LGU_ENCSTEM_WPACK_HALVES = 7 * 2 * 64 * 8 halves laid out [7 window rows ky][2 channel tiles ct][64 lanes l][8 halves
+ *   j], the B operand of v_mfma_f32_16x16x32_f16 as each lane loads it: a K step is one window row of 8 x-slots x 4
+ *   channels, and element j of lane l is w_h[16 ct + (l & 15)][j & 3][ky][2 (l >> 4) + (j >> 2)] where the channel j & 3 is
+ *   below 3 and the x-slot 2 (l >> 4) + (j >> 2) below 7, and ZERO in every other slot (the 4th channel and the 8th x-slot
+ *   are padding of the K dimension; the kernel zeroes them in its A operand as well).  16-byte aligned, otherwise
+ *   LGU_E_UNSUPPORTED.  bias: 32 halves.
+ * x, bias and out are served at the alignment of their element with the same bits: out is stored 8 bytes at a time where
+ *   Wo % 4 == 0 and the pointer is 8-byte aligned, by element otherwise.
+ * Every N >= 0, H >= 1, W >= 1 is served; N == 0: LGU_OK, nothing launched.  N < 0, H < 1, W < 1, an unknown flag, a null
+ * operand or one below its element's alignment: LGU_E_BADARG; Cin != 3 or Cout != 32, a pack that is not 16-byte aligned or
+ * more than INT_MAX workgroups (N * ceil(Wo / 32) * ceil(Ho / 4)): LGU_E_UNSUPPORTED.  Every refusal comes before any launch
+ * and writes nothing.  The operands travel in one parameter block passed by value. */
+#define LGU_ENCSTEM_WPACK_HALVES 7168
+#define LGU_ENCSTEM_X_HALF 1     /* flags: x holds IEEE half */
+#define LGU_ENCSTEM_RELU 2       /* flags: y = relu(y0) */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;   /* bias: 32 halves */
+  int N, H, W, Cin, Cout, flags;
+} lgu_encstem_args;
+int lgu_encstem7x7_h16(lgu_encstem_args args, void* stream);
+
+/* ---- the encoders' output layer: Conv2d(128, Cout, 1) + bias, Cout 128 (the feature encoder) or 256 (the context encoder),
+ * one launch, under float16 autocast (csrc/encends.hip).  Reference droid_slam/modules/extractor.py: conv2 of BasicEncoder;
+ * with LGU_ENCOUT_SPLIT also motion_filter.py:36-37, `net, inp = cnet(..).split([128,128], dim=2)`, `net.tanh()`, `inp.relu()`.
+ * x (N,128,H,W) NCHW contiguous IEEE half.  Rounding points (those of lgu_upmask1x1_c128_h16):
+ *   w_h = half(weight), b_h = half(bias)                    in the pack; x is half and used as it is
+ *   p   = sum over c of x[c] * w_h[co][c]                   exact products; fp32 accumulation from ZERO in four steps of 32
+ *                                                           channels, ascending
+ *   h   = half(b_h + p)                                     one fp32 addition, ONE rounding; NaN is kept
+ *   flags 0:           out (N,Cout,H,W) half = h; inp must be null
+ *   LGU_ENCOUT_SPLIT:  Cout == 256 only.  out (N,128,H,W) half = net = half(tanhf(float(h[:128]))): the device library's
+ *                      float tanh, one rounding, tanh(+-inf) = +-1, NaN kept; inp (N,128,H,W) half = h[128:] < 0 ? 0 :
+ *                      h[128:], NaN kept.  out and inp overlap neither x nor one another.
+ * The bits of a pixel depend on its own 128 inputs only: a NaN or infinite x reaches exactly its pixel's Cout outputs.  The
+ * outputs are fully written and nothing outside them.  No atomics, no workspace, no host synchronisation.
+ * wpack: 128 * Cout halves laid out [4 channel blocks kc][Cout/16 channel tiles ct][64 lanes l][8 halves j], the B operand of
+ *   v_mfma_f32_16x16x32_f16 as each lane loads it: element j of lane l is w_h[16 ct + (l & 15)][32 kc + 8 (l >> 4) + j].
+ *   Every slot holds a weight.  16-byte aligned, otherwise LGU_E_UNSUPPORTED.  bias: Cout halves.
+ * x, bias, out and inp are served at the alignment of their element with the same bits: the outputs are stored 8 bytes at a
+ *   time where H W % 4 == 0 and their pointers are 8-byte aligned, by element otherwise.
+ * Every N >= 0, H >= 1, W >= 1 is served; N == 0: LGU_OK, nothing launched.  N < 0, H < 1, W < 1, an unknown flag,
+ * LGU_ENCOUT_SPLIT with Cout != 256, a null x, wpack, bias or out, inp without the flag or the flag without inp, or an operand
+ * below its element's alignment: LGU_E_BADARG; Cin != 128, another Cout, a pack that is not 16-byte aligned, H W above
+ * INT_MAX - 64 or more than INT_MAX workgroups (N * ceil(H W / 64) * Cout / 64): LGU_E_UNSUPPORTED.  Every refusal comes before
+ * any launch and writes nothing.  The operands travel in one parameter block passed by value. */
+#define LGU_ENCOUT_SPLIT 1       /* flags: out = tanh(h[:128]), inp = relu(h[128:]) */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out; void* inp;   /* bias: Cout halves; inp: SPLIT only */
+  int N, H, W, Cin, Cout, flags;
+} lgu_encout_args;
+int lgu_encout1x1_c128_h16(lgu_encout_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,18 @@ class EncConvArgs(ctypes.Structure):
                 ("N", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int), ("flags", _int)]
 
 
+class EncStemArgs(ctypes.Structure):
+    """lgu_encstem_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int), ("Cin", _int),
+                ("Cout", _int), ("flags", _int)]
+
+
+class EncOutArgs(ctypes.Structure):
+    """lgu_encout_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("inp", _vp), ("N", _int), ("H", _int), ("W", _int),
+                ("Cin", _int), ("Cout", _int), ("flags", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -205,6 +217,11 @@ SIGNATURES = {
     # the encoders' residual-stage 3x3 convolutions with their tail and the 1x1 stride-2 branch: {x, wpack, bias, res, out,
     # dpack, dbias, r, N, H, W, Cin, Cout, stride, flags} by value, stream
     "lgu_encconv3x3_h16": [EncConvArgs, _vp],
+    # the encoders' stem, 7x7 stride 2, 3 -> 32: {x, wpack, bias, out, N, H, W, Cin, Cout, flags} by value, stream
+    "lgu_encstem7x7_h16": [EncStemArgs, _vp],
+    # the encoders' output 1x1, 128 -> 128 | 256, with the tanh / relu split: {x, wpack, bias, out, inp, N, H, W, Cin, Cout,
+    # flags} by value, stream
+    "lgu_encout1x1_c128_h16": [EncOutArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],

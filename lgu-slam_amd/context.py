@@ -4,10 +4,15 @@ droid_slam/modules/extractor.py) on the HIP kernels of csrc/encconv.hip.
 Without norms every tail of a residual-stage convolution is pointwise: bias, ReLU, residual add, ReLU.  Under float16
 autocast the module pays separate launches for each of them around each library convolution; here the twelve 3x3
 convolutions of layer1..3 are one `encconv.enc_conv3x3` launch each with the tail as its epilogue, and the two strided
-blocks get their 1x1 downsample branch from their first launch.  The stem (7x7, stride 2) and the output 1x1 stay the
-module's own calls.
+blocks get their 1x1 downsample branch from their first launch.  By default the stem (7x7, stride 2) and the output 1x1
+stay the module's own calls; with `ends=True` they are csrc/encends.hip's (`encconv.enc_stem7x7` with the ReLU,
+`encconv.enc_out1x1`): 14 launches per forward and no library convolution, opt-in because the bits are not the library's.
+`net_inp` gives the pair MotionFilter.track makes of the output, `tanh` of the first 128 planes and `relu` of the others,
+with `ends=True` from the output layer's own launch.
 
     context.install(net.cnet)                 # net.cnet(images) now reaches the fused path, state_dict unchanged
+    wr = context.install(net.cnet, ends=True) # the stem and the output layer too
+    net_, inp = wr.net_inp(images)            # = cnet(images).split([128,128], dim=2), .tanh(), .relu()
 
 The instance-norm feature encoder is `features.install`'s.
 """
@@ -48,14 +53,25 @@ class ContextEncoder:
     requires grad while grad mode is on and no dropout is active.  Everything else goes to the module's own forward
     unchanged: fp32, a bfloat16 autocast, CPU tensors, channels-last, gradients, a dropout in training mode.  Inside the
     fused path a convolution whose call is below encconv.MIN_FUSED_PIXELS of its shape is the module's convolution with
-    its tail in torch.  The packed weights are cached under each layer's weight and bias (data pointer, version, device):
+    its tail in torch.
+
+    ends=True: the stem is `encconv.enc_stem7x7(relu=True)` where conv1 takes 3 channels and the call has at least
+    encconv.MIN_STEM_PIXELS output pixels, and the output layer `encconv.enc_out1x1` where conv2 gives 128 or 256 planes and
+    the call has at least encconv.MIN_OUT_PIXELS of them: 14 launches and no Conv2d of the module.  The default, False, keeps
+    both the module's own calls.
+
+    `net_inp(images)` returns (tanh(ctx[:, :, :128]), relu(ctx[:, :, 128:])) of ctx = the encoder's output as two contiguous
+    (B,N,128,h,w) tensors (output_dim 256 only): with ends=True on the fused route the output layer's launch writes both,
+    on every other route it is this forward followed by torch's split, tanh and relu.
+
+    The packed weights are cached under each layer's weight and bias (data pointer, version, device):
     load_state_dict after install takes effect.  `fused_calls` counts the fused forwards.
 
     Construction refuses (RuntimeError naming the attribute) anything but conv1 (7x7, stride 2, to 32 channels) / an empty
     norm1 / layer1..3 of two residual blocks each with the channel counts and strides 32, 64 / 2, 128 / 2 and an empty
     nn.Sequential() at every norm site / the 1x1 conv2; an instance-norm encoder is pointed to features.install."""
 
-    def __init__(self, module):
+    def __init__(self, module, ends=False):
         conv1 = getattr(module, "conv1", None)
         if not isinstance(conv1, torch.nn.Conv2d):
             raise RuntimeError("ContextEncoder: conv1 must be a Conv2d")
@@ -90,6 +106,7 @@ class ContextEncoder:
             raise RuntimeError("ContextEncoder: conv2 must be a Conv2d")
         _check_conv(conv2, cin, conv2.out_channels, 1, 1, 0, "conv2")
         self.module = module
+        self.ends = bool(ends)
         self._packs = PackCache()
         self.fused_calls = 0
 
@@ -131,16 +148,28 @@ class ContextEncoder:
             return encconv.enc_conv3x3(t, self._packs.of(c2, encconv.pack_enc3), residual=r)
         return torch.relu(r + torch.relu(c2(t))).contiguous()
 
-    def _fused(self, x):
+    def _fused(self, x, split=False):
+        """The fused forward; with `split` the pair (net, inp) when the output layer's launch made it, else the output.  None
+        if the stem returned something the kernels do not take."""
         m = self.module
         b, n, c1, h1, w1 = x.shape
-        y = torch.relu(m.conv1(x.view(b * n, c1, h1, w1)))
-        if y.dtype != torch.float16:
-            return None
-        y = y.contiguous()
+        x4 = x.view(b * n, c1, h1, w1)
+        if self.ends and encconv.serves_stem(m.conv1, x4):
+            y = encconv.enc_stem7x7(x4, self._packs.of(m.conv1, encconv.pack_stem), relu=True)
+        else:
+            y = torch.relu(m.conv1(x4))
+            if y.dtype != torch.float16:
+                return None
+            y = y.contiguous()
         for blk in self.blocks:
             y = self._block(blk, y)
-        y = m.conv2(y)
+        if self.ends and encconv.serves_out(m.conv2, y):
+            pack = self._packs.of(m.conv2, encconv.pack_out1)
+            if split:
+                return tuple(t.view(b, n, 128, t.shape[2], t.shape[3]) for t in encconv.enc_out1x1(y, pack, split=True))
+            y = encconv.enc_out1x1(y, pack)
+        else:
+            y = m.conv2(y)
         return y.view(b, n, y.shape[1], y.shape[2], y.shape[3])
 
     def __call__(self, x):
@@ -151,12 +180,29 @@ class ContextEncoder:
         self.fused_calls += 1
         return out
 
+    def net_inp(self, x):
+        """(net, inp) = (tanh(ctx[:, :, :128]), relu(ctx[:, :, 128:])) of ctx = self(x), two contiguous (B,N,128,h,w) tensors
+        (reference motion_filter.py:36-37)."""
+        m = self.module
+        if m.conv2.out_channels != 256:
+            raise RuntimeError("ContextEncoder.net_inp: output_dim must be 256 (net and inp of 128 planes each), got %d"
+                               % m.conv2.out_channels)
+        out = self._fused(x, split=True) if self._serves(x) else None
+        if out is None:
+            out = type(m).forward(m, x)
+        else:
+            self.fused_calls += 1
+        if isinstance(out, tuple):
+            return out
+        net, inp = out.split([128, 128], dim=2)
+        return net.tanh().contiguous(), inp.relu().contiguous()
 
-def install(module):
+
+def install(module, ends=False):
     """Bind a ContextEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
-    unchanged), so every caller of the encoder reaches the fused path.  Returns the wrapper; a second call returns the
-    one already installed."""
-    return bind(module, "forward", ContextEncoder, lambda _: ContextEncoder(module))
+    unchanged), so every caller of the encoder reaches the fused path.  `ends` as in ContextEncoder.  Returns the wrapper;
+    a second call returns the one already installed (with the `ends` it was made with)."""
+    return bind(module, "forward", ContextEncoder, lambda _: ContextEncoder(module, ends=ends))
 
 
 def uninstall(module):

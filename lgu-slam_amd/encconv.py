@@ -11,9 +11,14 @@ convolution, the bias and that tail in one launch on the matrix cores, NCHW half
 shapes gives the block's 1x1 stride-2 downsample branch from the same launch (include/lgu_corr.h states the rounding
 points).  `context.ContextEncoder` and `features.FeatureEncoder(convs=True)` are its callers.
 
-`enc_conv3x3`: contiguous HIP device tensors only (no CPU fallback), every argument error raised before anything is
-launched, no host synchronisation (graph-capturable), forward only: an input that requires grad is refused while grad mode
-is on.  There is no fp32 kernel: fp32 evaluation is the module's own forward.
+The two ends of the same encoder, conv1 = Conv2d(3, 32, 7, stride=2, padding=3) and conv2 = Conv2d(128, Cout, 1), are
+`enc_stem7x7` and `enc_out1x1` (csrc/encends.hip), one launch each: the stem with the norm-free encoder's ReLU as its
+epilogue, the output layer with the context encoder's `net.tanh()` / `inp.relu()` split.  `ContextEncoder(ends=True)`
+and `FeatureEncoder(ends=True)` are their callers.
+
+`enc_conv3x3`, `enc_stem7x7`, `enc_out1x1`: contiguous HIP device tensors only (no CPU fallback), every argument error
+raised before anything is launched, no host synchronisation (graph-capturable), forward only: an input that requires grad
+is refused while grad mode is on.  There is no fp32 kernel: fp32 evaluation is the module's own forward.
 """
 import torch
 
@@ -32,6 +37,16 @@ RELU, RESIDUAL = 1, 2            # include/lgu_corr.h LGU_ENCCONV_RELU, LGU_ENCC
 # ContextEncoder and FeatureEncoder(convs=True) send such calls to the module's convolution.  0: every measured class (1
 # and 16 frames of 384x512) kept the fused path.
 MIN_FUSED_PIXELS = {shape: 0 for shape in SHAPES}
+
+STEM = (3, 32)                   # (Cin, Cout) of the 7x7 stride-2 stem
+OUT_CIN, OUT_COUTS = 128, (128, 256)
+X_HALF, STEM_RELU = 1, 2         # include/lgu_corr.h LGU_ENCSTEM_X_HALF, LGU_ENCSTEM_RELU
+SPLIT = 1                        # LGU_ENCOUT_SPLIT
+# The same rule for the two ends (tools/prof_encconv.py): output pixels N * Ho * Wo of the stem, and
+# N * H * W of the output layer per Cout, below which the module's own call is taken.  0: every measured class (1 and 16
+# frames of 384x512) kept the fused path.
+MIN_STEM_PIXELS = 0
+MIN_OUT_PIXELS = {128: 0, 256: 0}
 
 
 def _check_channels(weight, k, who):
@@ -161,3 +176,141 @@ def serves(conv, x):
         return False
     Ho, Wo = out_size(x.shape[2], x.shape[3], shape[2])
     return x.shape[0] * Ho * Wo >= MIN_FUSED_PIXELS[shape]
+
+
+def pack_stem(weight, bias):
+    """(wpack (7,2,64,8) half, bias_h (32) half) of the stem's Conv2d(3, 32, 7) weight (32,3,7,7) and bias (32), on the
+    weight's device.  A K step of v_mfma_f32_16x16x32_f16 is one window row ky of 8 x-slots x 4 channels:
+    wpack[ky, ct, l, j] = half(weight)[16 ct + (l & 15), j & 3, ky, 2 (l >> 4) + (j >> 2)] where the channel j & 3 < 3 and
+    the x-slot 2 (l >> 4) + (j >> 2) < 7, and 0 in every other slot (the 4th channel and the 8th x-slot pad the K step)."""
+    if weight.dim() != 4 or tuple(weight.shape) != (32, 3, 7, 7):
+        raise RuntimeError("pack_stem: weight must be (32,3,7,7), got %s" % (tuple(weight.shape),))
+    check_shape([(bias, "bias")], (32,))
+    with torch.no_grad():
+        wp = torch.zeros((32, 4, 7, 8), dtype=torch.float16, device=weight.device)
+        wp[:, :3, :, :7] = weight.detach().to(torch.float16)
+        # [ct][cl][ch][ky][g][s] -> [ky][ct][g][cl][s][ch]: lane l = 16 g + cl, element j = 4 s + ch, x-slot 2 g + s
+        wpack = wp.reshape(2, 16, 4, 7, 4, 2).permute(3, 0, 4, 1, 5, 2).reshape(7, 2, 64, 8)
+        bias_h = bias.detach().to(device=wp.device, dtype=torch.float16).contiguous()
+    return wpack.contiguous(), bias_h
+
+
+def pack_out1(weight, bias):
+    """(wpack (4,Cout/16,64,8) half, bias_h (Cout) half) of the output layer's Conv2d(128, Cout, 1) weight (Cout,128,1,1)
+    and bias (Cout), Cout 128 or 256, on the weight's device.
+    wpack[kc, ct, l, j] = half(weight)[16 ct + (l & 15), 32 kc + 8 (l >> 4) + j, 0, 0]: block kc of 32 input channels,
+    channel tile ct of 16 output channels, lane l, element j.  Every slot holds a weight."""
+    if weight.dim() != 4 or weight.shape[0] not in OUT_COUTS or tuple(weight.shape[1:]) != (OUT_CIN, 1, 1):
+        raise RuntimeError("pack_out1: weight must be (Cout,128,1,1) with Cout in %s, got %s" % (list(OUT_COUTS), tuple(weight.shape)))
+    cout = weight.shape[0]
+    check_shape([(bias, "bias")], (cout,))
+    with torch.no_grad():
+        wh = weight.detach().to(torch.float16)
+        # [ct][cl][kc][g][j] -> [kc][ct][g][cl][j]
+        wpack = wh.reshape(cout // 16, 16, 4, 4, 8).permute(2, 0, 3, 1, 4).reshape(4, cout // 16, 64, 8)
+        bias_h = bias.detach().to(device=wh.device, dtype=torch.float16).contiguous()
+    return wpack.contiguous(), bias_h
+
+
+def enc_stem7x7(x, pack, relu=False):
+    """The stem Conv2d(3, 32, 7, stride=2, padding=3) of x (N,3,H,W), float32 or half, with `pack` = (wpack, bias_h) of
+    `pack_stem`, as a new (N,32,Ho,Wo) half tensor, (Ho, Wo) = out_size(H, W, 2):
+
+        y0 = half(b_h + sum half(x) * w_h)    exact products, fp32 accumulation from the bias, window rows ascending, one
+                                              rounding; padding, the row or column past an odd size included, is exact zeros
+        y  = y0 | relu(y0)                    relu=False (what an instance norm reads) | relu=True.  NaN is kept.
+
+    A half x gives the bits of the float32 x it is the rounding of.  Refusals, in this order, all before anything is
+    launched: x not 4-D, pack not a pair, bias_h not 1-D, (Cin, Cout) not (3, 32) (UnsupportedShape), the size of wpack, then
+    contiguity, dtypes (x float32 or half, the pack half), grad and device of x, wpack, bias_h in that order
+    (_host.check_layer_operands); then N == 0 returns the empty result and H*W == 0 raises.  x and bias_h are served at
+    element alignment; a pack that is not 16-byte aligned (never the case for what pack_stem returns) raises
+    UnsupportedShape."""
+    if x.dim() != 4:
+        raise RuntimeError("x must be (N,3,H,W), got %s" % (tuple(x.shape),))
+    if not isinstance(pack, (tuple, list)) or len(pack) != 2:
+        raise RuntimeError("pack must be (wpack, bias_h) of pack_stem")
+    wpack, bias_h = pack
+    if bias_h.dim() != 1:
+        raise RuntimeError("bias_h must be (Cout,), got %s" % (tuple(bias_h.shape),))
+    N, cin, H, W = x.shape
+    cout = bias_h.shape[0]
+    if (cin, cout) != STEM:
+        raise _lib.UnsupportedShape("enc_stem7x7 serves (Cin, Cout) = (3, 32), got (%d, %d)" % (cin, cout))
+    if wpack.numel() != 7 * 2 * 64 * 8:
+        raise RuntimeError("wpack must hold %d halves (pack_stem), got %s" % (7 * 2 * 64 * 8, tuple(wpack.shape)))
+    check_layer_operands("enc_stem7x7", [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")])
+    Ho, Wo = out_size(H, W, 2)
+    out = torch.empty((N, cout, Ho, Wo), dtype=torch.float16, device=x.device)
+    if N > 0:
+        if H * W == 0:
+            raise RuntimeError("enc_stem7x7: empty frame (H*W = 0)")
+        flags = (X_HALF if x.dtype == torch.float16 else 0) | (STEM_RELU if relu else 0)
+        args = _lib.EncStemArgs(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), N, H, W, cin, cout, flags)
+        launch("lgu_encstem7x7_h16", "enc_stem7x7", x.device, args, _stream(x))
+    return out
+
+
+def enc_out1x1(x, pack, split=False):
+    """The output layer Conv2d(128, Cout, 1) of half x (N,128,H,W) with `pack` = (wpack, bias_h) of `pack_out1` (the bias
+    gives Cout, 128 or 256):
+
+        h = half(b_h + sum_c x[c] * w_h[co, c])    exact products, fp32 accumulation from zero in four blocks of 32 channels,
+                                                   one addition of the bias, one rounding.  NaN is kept.
+
+    split=False returns h as a new (N,Cout,H,W) half tensor.  split=True (Cout 256) returns (net, inp), two new (N,128,H,W)
+    half tensors: net = half(tanh(float(h[:, :128]))) (tanh(+-inf) = +-1), inp = relu(h[:, 128:]).
+
+    Refusals, in this order, all before anything is launched: x not 4-D, pack not a pair, bias_h not 1-D, Cin not 128 or
+    Cout not 128 or 256 (UnsupportedShape), split with Cout 128, the size of wpack, x not half, then contiguity, dtypes
+    (half), grad and device of x, wpack, bias_h in that order (_host.check_layer_operands); then N == 0 returns the empty
+    result and H*W == 0 raises.  x and bias_h are served at element alignment; a pack that is not 16-byte aligned raises
+    UnsupportedShape."""
+    if x.dim() != 4:
+        raise RuntimeError("x must be (N,128,H,W), got %s" % (tuple(x.shape),))
+    if not isinstance(pack, (tuple, list)) or len(pack) != 2:
+        raise RuntimeError("pack must be (wpack, bias_h) of pack_out1")
+    wpack, bias_h = pack
+    if bias_h.dim() != 1:
+        raise RuntimeError("bias_h must be (Cout,), got %s" % (tuple(bias_h.shape),))
+    N, cin, H, W = x.shape
+    cout = bias_h.shape[0]
+    if cin != OUT_CIN or cout not in OUT_COUTS:
+        raise _lib.UnsupportedShape("enc_out1x1 serves Cin = 128 and Cout in %s, got (%d, %d)" % (list(OUT_COUTS), cin, cout))
+    if split and cout != 256:
+        raise RuntimeError("split=True (net, inp of 128 planes each) needs Cout = 256, got %d" % cout)
+    if wpack.numel() != cin * cout:
+        raise RuntimeError("wpack must hold %d halves (pack_out1, 128 -> %d), got %s" % (cin * cout, cout, tuple(wpack.shape)))
+    check_dtype([(x, "x")], torch.float16)
+    check_layer_operands("enc_out1x1", [(x, "x"), (wpack, "wpack"), (bias_h, "bias_h")])
+    out = torch.empty((N, 128 if split else cout, H, W), dtype=torch.float16, device=x.device)
+    inp = torch.empty_like(out) if split else None
+    if N > 0:
+        if H * W == 0:
+            raise RuntimeError("enc_out1x1: empty frame (H*W = 0)")
+        args = _lib.EncOutArgs(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), inp.data_ptr() if split else None,
+                               N, H, W, cin, cout, SPLIT if split else 0)
+        launch("lgu_encout1x1_c128_h16", "enc_out1x1", x.device, args, _stream(x))
+    return (out, inp) if split else out
+
+
+def serves_stem(conv, x):
+    """A call of `conv` on the NCHW tensor x takes the fused stem: conv is Conv2d(3, 32, 7, stride=2, padding=3) with a bias
+    and the call has at least MIN_STEM_PIXELS output pixels (read at the call)."""
+    if not is_conv(conv, STEM[0], STEM[1], 7, stride=2, pad=3, bias=True):
+        return False
+    if x.dim() != 4 or x.shape[1] != STEM[0] or x.shape[2] * x.shape[3] == 0:
+        return False
+    Ho, Wo = out_size(x.shape[2], x.shape[3], 2)
+    return x.shape[0] * Ho * Wo >= MIN_STEM_PIXELS
+
+
+def serves_out(conv, x):
+    """A call of `conv` on the half NCHW tensor x takes the fused output layer: conv is Conv2d(128, Cout, 1) with a bias,
+    Cout 128 or 256, and the call has at least MIN_OUT_PIXELS[Cout] pixels (read at the call)."""
+    cout = getattr(conv, "out_channels", None)
+    if cout not in OUT_COUTS or not is_conv(conv, OUT_CIN, cout, 1, bias=True):
+        return False
+    if x.dim() != 4 or x.shape[1] != OUT_CIN or x.shape[2] * x.shape[3] == 0:
+        return False
+    return x.shape[0] * x.shape[2] * x.shape[3] >= MIN_OUT_PIXELS[cout]

@@ -5,7 +5,8 @@ csrc/instnorm.hip.
 By default the 13 convolutions stay the module's own calls (MIOpen); with `convs=True` the twelve 3x3 convolutions of
 layer1..3 go through csrc/encconv.hip under float16 autocast (`encconv.enc_conv3x3`, identity epilogue, the 1x1 downsample
 branch of a strided block from its first launch), opt-in because the library's summation order differs and
-`features.install(m)` keeps its bits.  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
+`features.install(m)` keeps its bits; with `ends=True` the stem and the output 1x1 go through csrc/encends.hip
+(`encconv.enc_stem7x7`, `encconv.enc_out1x1`), opt-in for the same reason and independent of `convs`.  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
 6 residual add + ReLU pairs, becomes one call per site group, 13 per forward: each convolution output is read once, the
 statistics are taken in fp32 from the stored values, and the block output is rounded to the tensor type once.  A call
 is one launch while H*W <= resident_limit(dtype): every site of a 384x512 frame under float16 autocast (13 launches).
@@ -149,10 +150,16 @@ class FeatureEncoder:
     encconv.MIN_FUSED_PIXELS of its shape and the layer has one of the kernel's shapes; the instance-norm calls are the
     same.  The fp32 path does not change.  The default, False, keeps every convolution the module's own.
 
+    ends=True: under float16 autocast the stem is `encconv.enc_stem7x7` with the identity epilogue (norm1's call reads it)
+    where conv1 is Conv2d(3, 32, 7, stride=2, padding=3) with a bias and the call has at least encconv.MIN_STEM_PIXELS output
+    pixels, and the output layer `encconv.enc_out1x1` where conv2 has a bias and gives 128 or 256 planes and the call has at
+    least encconv.MIN_OUT_PIXELS of them (csrc/encends.hip); the instance-norm calls are the same.  Independent of `convs`;
+    the fp32 path does not change.  The default, False, keeps both the module's own.
+
     Construction refuses (RuntimeError naming the attribute) anything but conv1 / norm1 / layer1..3 of two residual
     blocks each / conv2 with InstanceNorm2d(affine=False, track_running_stats=False) at every norm site."""
 
-    def __init__(self, module, convs=False):
+    def __init__(self, module, convs=False, ends=False):
         conv1 = getattr(module, "conv1", None)
         if not isinstance(conv1, torch.nn.Conv2d):
             raise RuntimeError("FeatureEncoder: conv1 must be a Conv2d")
@@ -195,6 +202,7 @@ class FeatureEncoder:
         _check_conv(conv2, cin, conv2.out_channels, 1, 1, 0, "conv2")
         self.module = module
         self.convs = bool(convs)
+        self.ends = bool(ends)
         self._packs = PackCache()
         self.fused_calls = 0
 
@@ -229,7 +237,12 @@ class FeatureEncoder:
         def ok(t):      # what instance_norm_relu would check; the shapes follow from the architecture
             return t.dtype == dt and t.is_contiguous() and t.shape[2] * t.shape[3] > 1 and not t.requires_grad
 
-        y = m.conv1(x.view(b * n, c1, h1, w1))
+        x4 = x.view(b * n, c1, h1, w1)
+        ends = self.ends and dt == torch.float16      # the stem and the output layer on csrc/encends.hip
+        if ends and encconv.serves_stem(m.conv1, x4):
+            y = encconv.enc_stem7x7(x4, self._packs.of(m.conv1, encconv.pack_stem))
+        else:
+            y = m.conv1(x4)
         if not ok(y):
             return None
         y = _instnorm(y, None, y, 0, m.norm1.eps)
@@ -261,7 +274,10 @@ class FeatureEncoder:
                 if not ok(r):
                     return None
                 y = _instnorm(t, r, t, 2, blk.norm2.eps)
-        y = m.conv2(y)
+        if ends and encconv.serves_out(m.conv2, y):
+            y = encconv.enc_out1x1(y, self._packs.of(m.conv2, encconv.pack_out1))
+        else:
+            y = m.conv2(y)
         return y.view(b, n, y.shape[1], y.shape[2], y.shape[3])
 
     def __call__(self, x):
@@ -276,11 +292,11 @@ class FeatureEncoder:
         return out
 
 
-def install(module, convs=False):
+def install(module, convs=False, ends=False):
     """Bind a FeatureEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
-    unchanged), so every caller of the encoder reaches the fused path.  `convs` as in FeatureEncoder.  Returns the
-    wrapper; a second call returns the one already installed (with the `convs` it was made with)."""
-    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module, convs=convs))
+    unchanged), so every caller of the encoder reaches the fused path.  `convs` and `ends` as in FeatureEncoder.  Returns
+    the wrapper; a second call returns the one already installed (with the `convs` and `ends` it was made with)."""
+    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module, convs=convs, ends=ends))
 
 
 def uninstall(module):

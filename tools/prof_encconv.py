@@ -10,14 +10,23 @@ Forms, per workload:
   <Cin>-<Cout>-s2/down              enc_conv3x3(x, relu=True, down=..)  against enc_conv3x3(x, relu=True) + the module's 1x1
   cnet                              context.install(cnet)               against the module's own forward
   fnet_convs                        features.install(fnet, convs=True)  against features.install(fnet)
+and with --ends the two ends of the encoders (csrc/encends.hip), written to profiles/encends_prof.json:
+  stem/relu                         enc_stem7x7(x, relu=True)           against relu_(conv1(x))
+  stem/bare                         enc_stem7x7(x)                      against conv1(x)
+  out128, out256                    enc_out1x1(x)                       against conv2(x) of fnet / cnet
+  net_inp                           enc_out1x1(x, split=True)           against conv2(x).split + tanh + relu
+  cnet_ends                         ContextEncoder(cnet, ends=True)     against ContextEncoder(cnet)
+  fnet_ends                         FeatureEncoder(fnet, convs=True, ends=True)  against FeatureEncoder(fnet, convs=True)
 Each layer form runs at the plane its layer sees in a 384x512 frame (32 channels: 192x256, 64: 96x128, 128: 48x64).
 Method (tools/prof_conv3.py's): every timed call runs on the next of ROT disjoint input sets, the two sides alternate call
 by call in one process, and a spin kernel ahead of the first event keeps the host's enqueue time out of the window.
 Reported per side: median, quartiles and spread = p75 - p25 (ms).  `keep_fused`: fused median + spread < other median -
-spread.  `min_fused_pixels`: per shape, the smallest number of output pixels N*Ho*Wo from which every measured class of
+spread.  `min_stem_pixels` / `min_out_pixels` (--ends): the same rule for encconv.MIN_STEM_PIXELS and MIN_OUT_PIXELS.  `min_fused_pixels`: per shape, the smallest number of output pixels N*Ho*Wo from which every measured class of
 every layer form of the shape keeps the fused path, the rule by which lgu_slam_amd.encconv.MIN_FUSED_PIXELS is set (0:
 every class keeps it).
-Usage: prof_encconv.py [--reps N] [--out PATH] [--forms a,b] [--frames 1,16]
+--spin CYCLES lengthens the spin kernel: a whole forward at one frame is 14 to 27 launches whose enqueue outlasts the default
+spin, so its window then holds host time too (a bimodal sample); 2000000 cycles hide it.
+Usage: prof_encconv.py [--ends] [--reps N] [--out PATH] [--forms a,b] [--frames 1,16] [--spin CYCLES]
 """
 import argparse
 import json
@@ -53,6 +62,8 @@ def layer_forms():
 
 
 FORMS = layer_forms() + ["cnet", "fnet_convs"]
+END_FORMS = ["stem/relu", "stem/bare", "out128", "out256", "net_inp", "cnet_ends", "fnet_ends"]
+OUT_ENDS = os.path.join(ROOT, "profiles", "encends_prof.json")
 
 
 def stats(ts):
@@ -76,6 +87,32 @@ def sides_of(form, cnet, fnet, fnet_twin, frames):
     if form == "fnet_convs":
         xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
         return lgu_slam_amd.features.FeatureEncoder(fnet_twin, convs=True), lgu_slam_amd.features.FeatureEncoder(fnet), xs
+    if form in ("cnet_ends", "fnet_ends"):
+        xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
+        if form == "cnet_ends":
+            twin = RC.make_case("context_cnet_2x40x56")[0].cuda()
+            return lgu_slam_amd.context.ContextEncoder(twin, ends=True), lgu_slam_amd.context.ContextEncoder(cnet), xs
+        return (lgu_slam_amd.features.FeatureEncoder(fnet_twin, convs=True, ends=True),
+                lgu_slam_amd.features.FeatureEncoder(fnet, convs=True), xs)
+    if form.startswith("stem/"):
+        conv = cnet.conv1
+        pack = E.pack_stem(conv.weight, conv.bias)
+        xs = [RF.make_images(100 + i, frames, *FRAME)[0].contiguous().cuda() for i in range(ROT)]
+        if form == "stem/relu":
+            return (lambda x: E.enc_stem7x7(x, pack, relu=True)), (lambda x: torch.relu_(conv(x))), xs
+        return (lambda x: E.enc_stem7x7(x, pack)), conv, xs
+    if form in ("out128", "out256", "net_inp"):
+        conv = fnet.conv2 if form == "out128" else cnet.conv2
+        pack = E.pack_out1(conv.weight, conv.bias)
+        g = torch.Generator().manual_seed(7 + 128)
+        xs = [(torch.randn((frames, 128) + PLANE[128], generator=g) * 2.0).clamp_(min=0.0).half().cuda() for _ in range(ROT)]
+        if form != "net_inp":
+            return (lambda x: E.enc_out1x1(x, pack)), conv, xs
+
+        def torch_tail(x):
+            net, inp = conv(x).split([128, 128], dim=1)
+            return net.tanh(), inp.relu()
+        return (lambda x: E.enc_out1x1(x, pack, split=True)), torch_tail, xs
     name, tail = form.split("/")
     shape = [s for s in E.SHAPES if sid(s) == name][0]
     cin, cout, st = shape
@@ -132,7 +169,12 @@ def measure(reps, forms, frames_list):
                 f, o = stats(ts["fused"]), stats(ts["other"])
                 d = {"fused": f, "other": o, "speedup": o["median_ms"] / f["median_ms"],
                      "keep_fused": bool(f["median_ms"] + f["spread_ms"] < o["median_ms"] - o["spread_ms"])}
-                if "/" in form:
+                if form.startswith("stem/"):
+                    ho, wo = E.out_size(*FRAME, 2)
+                    d["out_pixels"] = frames * ho * wo
+                elif form in ("out128", "out256", "net_inp"):
+                    d["out_pixels"] = frames * PLANE[128][0] * PLANE[128][1]
+                elif "/" in form:
                     shape = [s for s in E.SHAPES if sid(s) == form.split("/")[0]][0]
                     ho, wo = E.out_size(*PLANE[shape[0]], shape[2])
                     d["out_pixels"] = frames * ho * wo
@@ -160,21 +202,45 @@ def thresholds(workloads):
     return out
 
 
+def threshold_of(workloads, forms):
+    """The rule of `thresholds` over the classes of the named forms."""
+    per = {}
+    for w in workloads.values():
+        for form, d in w["forms"].items():
+            if form in forms:
+                per[d["out_pixels"]] = per.get(d["out_pixels"], True) and d["keep_fused"]
+    classes = sorted(per.items())
+    need = 0
+    for i, (pixels, keep) in enumerate(classes):
+        if not keep:
+            need = classes[i + 1][0] if i + 1 < len(classes) else 1 << 62
+    return need
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=40)
-    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--ends", action="store_true", help="time the stem and the output layer (csrc/encends.hip) instead: "
+                    "profiles/encends_prof.json")
+    ap.add_argument("--out")
     ap.add_argument("--forms", help="comma-separated subset of the forms to time (e.g. a variant library under LGU_LIB_PATH); "
                     "no thresholds are derived from a subset")
     ap.add_argument("--frames", default="1,16")
+    ap.add_argument("--spin", type=int, default=SPIN, help="cycles of the spin kernel ahead of each timed call")
     args = ap.parse_args()
+    globals()["SPIN"] = args.spin
     lgu_slam_amd._lib.load()
     E.MIN_FUSED_PIXELS = {s: 0 for s in E.SHAPES}      # measure the fused path at every class; the rule is applied afterwards
-    forms = args.forms.split(",") if args.forms else list(FORMS)
+    E.MIN_STEM_PIXELS, E.MIN_OUT_PIXELS = 0, {c: 0 for c in E.OUT_COUTS}
+    args.out = args.out or (OUT_ENDS if args.ends else OUT)
+    forms = args.forms.split(",") if args.forms else list(END_FORMS if args.ends else FORMS)
     workloads = measure(args.reps, forms, [int(f) for f in args.frames.split(",")])
     doc = {"tool": "prof_encconv", "device": torch.cuda.get_device_name(0), "lib": lgu_slam_amd._lib.version(),
-           "reps": args.reps, "rotation": ROT, "workloads": workloads}
-    if not args.forms:
+           "reps": args.reps, "rotation": ROT, "spin_cycles": args.spin, "workloads": workloads}
+    if not args.forms and args.ends:
+        doc["min_stem_pixels"] = threshold_of(workloads, ("stem/relu", "stem/bare"))
+        doc["min_out_pixels"] = {"128": threshold_of(workloads, ("out128",)), "256": threshold_of(workloads, ("out256", "net_inp"))}
+    elif not args.forms:
         doc["min_fused_pixels"] = thresholds(workloads)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     json.dump(doc, open(args.out, "w"), indent=1, sort_keys=True)
