@@ -1125,6 +1125,84 @@ typedef struct {
 } lgu_encout_args;
 int lgu_encout1x1_c128_h16(lgu_encout_args args, void* stream);
 
+/* ---- the feature encoder's instance norms folded into its residual-stage convolutions (csrc/encconv.hip, csrc/encstats.hpp).
+ * Reference droid_slam/modules/extractor.py:49-55: relu(norm1(conv1 x)), relu(norm2(conv2 .)), relu(x + .) of a ResidualBlock
+ * with norm_fn='instance' (InstanceNorm2d without affine terms or running statistics, biased variance).  The producer
+ * convolution adds exact sums of its stored half outputs to per-plane accumulators (EMIT); the consumer convolution
+ * normalises while it stages its input (the prologue) and, where the staged tensor is a residual later, writes it out once
+ * (keep).  The bits are NOT those of lgu_instnorm_relu_h16 (whose statistics are fp32 tree sums): the folded route is opt-in.
+ *
+ * Exact plane statistics.  A finite half h is m 2^(k-24) with integers 0 <= m < 2048, 0 <= k <= 29, so xi = h 2^24 is an
+ * integer, |xi| < 2^40, and xi^2 = m^2 << 2k is below 2^80.  The accumulator of a plane (n, c) is R slots of four 64-bit
+ * integers, a tensor (N,C,R,4) int64, ZERO on entry (accumulated into a caller-zeroed buffer, the rule of volume_grad) and
+ * 8-byte aligned, R = lgu_encstats_replicas() (8):
+ *   S1  = sum xi (two's complement)   LO = sum (xi^2 mod 2^40)   HI = sum (xi^2 >> 40)   BAD = number of non-finite values
+ * A workgroup reduces its tile over lanes first and issues one integer atomic add per channel and word (vector-memory
+ * atomics, global_atomic_add_x2; BAD only where it is not zero) into slot = (its tile index) mod R.  Integer sums do not
+ * depend on their order: summed over the R slots the four words are exact and the same for every schedule, tile choice and R.
+ * Planes of more than 2^22 pixels: LGU_E_UNSUPPORTED (each word stays below 2^62 up to there).
+ *
+ * Mean and rstd: ONE device function, used by the prologue and by lgu_encstats_finalize; double arithmetic, every step
+ * rounded once, in this order (IEEE division and square root, no contraction; the same lines in numpy give the same bits):
+ *   S1, LO, HI, BAD = integer sums over the R slots
+ *   a    = double(S1)                      q   = double(HI) * 2^40 + double(LO)           cnt = pixels per plane
+ *   mean = float(a / (cnt * 2^24))         var = max((q - (a * a) / cnt) / (cnt * 2^48), 0)
+ *   rstd = float(1 / sqrt(var + double(eps)))
+ *   BAD != 0: mean = rstd = NaN            (PyTorch's instance norm makes such a plane NaN)
+ * lgu_encstats_finalize({acc, mean_rstd, planes, cnt, eps}, stream) writes (planes,2) float32 {mean, rstd} from acc
+ * (planes,R,4); like every layer entry it takes its operands in one parameter block passed by value.  planes == 0: LGU_OK, nothing launched.  planes < 0, cnt < 1, eps < 0 or NaN, a null pointer, acc below
+ * 8-byte or mean_rstd below 4-byte alignment: LGU_E_BADARG; cnt > 2^22: LGU_E_UNSUPPORTED.
+ *
+ * lgu_encconv3x3_norm_h16: x, wpack, bias, out, dpack, dbias, r, N, H, W, Cin, Cout, stride as lgu_encconv3x3_h16, with the
+ * identity epilogue always.  mode names the prologue, applied to every staged pixel INSIDE the image; a pixel outside the
+ * image is zero AFTER the prologue (the padding belongs to the normalised tensor):
+ *   IN(v; mu, rho) = (float(v) - mu) * rho       an fp32 subtraction, then an fp32 product, no contraction
+ *   relu(v)        = v < 0 ? 0 : v               a NaN is kept
+ *   LGU_ENCNORM_NONE      h = x                                                      (EMIT only)
+ *   LGU_ENCNORM_NORM      h = half(relu(IN(x; mu_x, rho_x)))                         extractor.py:49-50
+ *   LGU_ENCNORM_RES       h = half(relu(float(y) + relu(IN(x; mu_x, rho_x))))        :50, :55, no downsample
+ *   LGU_ENCNORM_RES_NORM  h = half(relu(IN(y; mu_y, rho_y) + relu(IN(x; mu_x, rho_x))))   :50-55, with downsample.1
+ * (mu_x, rho_x) per plane of x from stats_x (N,Cin,R,4) with cnt = H W and eps, (mu_y, rho_y) from stats_y; y (N,Cin,H,W)
+ * half.  ONE rounding to half; the add is an fp32 add of its own.  h is what the convolution (and on a strided launch the
+ * 1x1 branch) then sees: from there on out and r have the bits of lgu_encconv3x3_h16 on h with flags 0.  Each workgroup fills
+ * a (mean, rstd) table in LDS from the accumulators at its start; the producer is an earlier launch on the same stream, no
+ * workgroup waits on another and there are no fences.
+ * keep (N,Cin,H,W) half, with a prologue only: h is also written there, each pixel once, by the workgroup of channel group 0
+ *   whose output tile (TY rows from y0, TX columns from x0) owns it: input rows [s y0, s (y0 + TY)), columns [s x0, s (x0 +
+ *   TX)), clipped to the image.  keep overlaps no operand (other workgroups read their halo).  Fully written, nothing outside.
+ * LGU_ENCNORM_EMIT: the sums of the stored half output over its pixels (y < Ho, x < Wo only) are added to stats_out
+ *   (N,Cout,R,4), and on a launch with the branch those of r to stats_r.  Emitting changes no bit of out or r.
+ * The bits of out, r and keep depend on the image, its accumulators, H and W only: not on N, the batch position or the tile.
+ * A plane with BAD != 0 makes h NaN over that whole plane (for RES_NORM also y's plane), and with it every output that
+ * reads it.
+ * Refusals and alignment follow lgu_encconv3x3_h16; further LGU_E_BADARG: mode outside 0..3, an unknown flag, eps < 0 or NaN,
+ * LGU_ENCNORM_NONE without LGU_ENCNORM_EMIT (that call is lgu_encconv3x3_h16), stats_x / y / stats_y not exactly those the
+ * mode reads, keep without a prologue, stats_out not given exactly with EMIT, stats_r not given exactly with EMIT and the
+ * branch, an accumulator below 8-byte alignment; H W > 2^22: LGU_E_UNSUPPORTED.  Every refusal comes before any launch and
+ * writes nothing.  The operands travel in one parameter block passed by value; lgu_encconv_args is unchanged. */
+#define LGU_ENCNORM_NONE 0
+#define LGU_ENCNORM_NORM 1
+#define LGU_ENCNORM_RES 2
+#define LGU_ENCNORM_RES_NORM 3
+#define LGU_ENCNORM_EMIT 1       /* flags: add the sums of out (and r) to stats_out (and stats_r) */
+typedef struct {
+  const void* x; const void* wpack; const void* bias; void* out;      /* bias: Cout halves */
+  const void* dpack; const void* dbias; void* r;                      /* all three, or all null */
+  const void* y; const void* stats_x; const void* stats_y;            /* what the mode reads, null otherwise */
+  void* keep;                                                         /* or null */
+  void* stats_out; void* stats_r;                                     /* EMIT (stats_r: with the branch), null otherwise */
+  float eps;
+  int N, H, W, Cin, Cout, stride, mode, flags;
+} lgu_encconv_norm_args;
+int lgu_encconv3x3_norm_h16(lgu_encconv_norm_args args, void* stream);
+typedef struct {
+  const void* acc; void* mean_rstd;   /* (planes,R,4) int64 in, (planes,2) float32 out */
+  long planes, cnt;
+  float eps;
+} lgu_encstats_args;
+int lgu_encstats_finalize(lgu_encstats_args args, void* stream);
+int lgu_encstats_replicas(void);
+
 #ifdef __cplusplus
 }
 #endif

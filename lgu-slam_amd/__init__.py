@@ -16,7 +16,7 @@ from .conv1 import Conv1  # noqa: F401
 from .conv3 import Conv3, Conv3Stack, conv3x3_fanout  # noqa: F401
 from .context import ContextEncoder  # noqa: F401
 from .corr import AltCorrBlock, CorrBlock, CorrSampler, DefCorrSampler, per_Corr_Normalization  # noqa: F401
-from .encconv import enc_conv3x3, enc_out1x1, enc_stem7x7, pack_enc1, pack_enc3, pack_out1, pack_stem  # noqa: F401
+from .encconv import enc_conv3x3, enc_conv3x3_norm, enc_out1x1, enc_stem7x7, pack_enc1, pack_enc3, pack_out1, pack_stem  # noqa: F401
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
 from .flow import FlowEncoder  # noqa: F401

@@ -73,6 +73,18 @@ class EncConvArgs(ctypes.Structure):
                 ("N", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int), ("flags", _int)]
 
 
+class EncConvNormArgs(ctypes.Structure):
+    """lgu_encconv_norm_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("dpack", _vp), ("dbias", _vp), ("r", _vp), ("y", _vp),
+                ("stats_x", _vp), ("stats_y", _vp), ("keep", _vp), ("stats_out", _vp), ("stats_r", _vp), ("eps", ctypes.c_float),
+                ("N", _int), ("H", _int), ("W", _int), ("Cin", _int), ("Cout", _int), ("stride", _int), ("mode", _int), ("flags", _int)]
+
+
+class EncStatsArgs(ctypes.Structure):
+    """lgu_encstats_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("acc", _vp), ("mean_rstd", _vp), ("planes", ctypes.c_long), ("cnt", ctypes.c_long), ("eps", ctypes.c_float)]
+
+
 class EncStemArgs(ctypes.Structure):
     """lgu_encstem_args of include/lgu_corr.h, passed by value."""
     _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("out", _vp), ("N", _int), ("H", _int), ("W", _int), ("Cin", _int),
@@ -217,6 +229,12 @@ SIGNATURES = {
     # the encoders' residual-stage 3x3 convolutions with their tail and the 1x1 stride-2 branch: {x, wpack, bias, res, out,
     # dpack, dbias, r, N, H, W, Cin, Cout, stride, flags} by value, stream
     "lgu_encconv3x3_h16": [EncConvArgs, _vp],
+    # the same convolutions with the feature encoder's instance norms folded in: {x, wpack, bias, out, dpack, dbias, r, y,
+    # stats_x, stats_y, keep, stats_out, stats_r, eps, N, H, W, Cin, Cout, stride, mode, flags} by value, stream
+    "lgu_encconv3x3_norm_h16": [EncConvNormArgs, _vp],
+    # {acc, mean_rstd, planes, cnt, eps} by value, stream
+    "lgu_encstats_finalize": [EncStatsArgs, _vp],
+    "lgu_encstats_replicas": [],
     # the encoders' stem, 7x7 stride 2, 3 -> 32: {x, wpack, bias, out, N, H, W, Cin, Cout, flags} by value, stream
     "lgu_encstem7x7_h16": [EncStemArgs, _vp],
     # the encoders' output 1x1, 128 -> 128 | 256, with the tanh / relu split: {x, wpack, bias, out, inp, N, H, W, Cin, Cout,

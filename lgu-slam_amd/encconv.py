@@ -16,14 +16,19 @@ The two ends of the same encoder, conv1 = Conv2d(3, 32, 7, stride=2, padding=3) 
 epilogue, the output layer with the context encoder's `net.tanh()` / `inp.relu()` split.  `ContextEncoder(ends=True)`
 and `FeatureEncoder(ends=True)` are their callers.
 
-`enc_conv3x3`, `enc_stem7x7`, `enc_out1x1`: contiguous HIP device tensors only (no CPU fallback), every argument error
+The feature encoder's instance norms fold into the same launches (`enc_conv3x3_norm`): the producer convolution adds exact
+integer sums of its stored outputs to per-plane accumulators (`new_stats`), the consumer normalises while it stages its
+input and writes the staged tensor out where it is a residual later; `stats_mean_rstd` is the (mean, rstd) the consumer
+forms.  `features.FeatureEncoder(convs=True, norms=True)` is the caller.
+
+`enc_conv3x3`, `enc_conv3x3_norm`, `enc_stem7x7`, `enc_out1x1`: contiguous HIP device tensors only (no CPU fallback), every argument error
 raised before anything is launched, no host synchronisation (graph-capturable), forward only: an input that requires grad
 is refused while grad mode is on.  There is no fp32 kernel: fp32 evaluation is the module's own forward.
 """
 import torch
 
 from . import _lib
-from ._host import check_dtype, check_layer_operands, check_shape, is_conv, launch
+from ._host import check_contiguous, check_device, check_dtype, check_layer_operands, check_no_grad, check_shape, is_conv, launch
 from ._host import stream as _stream
 
 # (Cin, Cout, stride) of Conv2d(Cin, Cout, 3, stride, padding=1) the kernel serves
@@ -37,6 +42,17 @@ RELU, RESIDUAL = 1, 2            # include/lgu_corr.h LGU_ENCCONV_RELU, LGU_ENCC
 # ContextEncoder and FeatureEncoder(convs=True) send such calls to the module's convolution.  0: every measured class (1
 # and 16 frames of 384x512) kept the fused path.
 MIN_FUSED_PIXELS = {shape: 0 for shape in SHAPES}
+
+# FeatureEncoder(norms=True): the pixels N * H * W of the images below which the folded route (the instance norms inside
+# the twelve convolutions) is not taken and the per-site route runs.  Set from the measurement of tools/prof_encconv.py
+# --norms: 0 only for classes where the folded forward beat the per-site one beyond both spreads.
+# 1 << 62: neither measured class (1 and 16 frames of 384x512) did, the folded forward is the slower one at both, so
+# norms=True keeps today's route until a caller lowers this.
+MIN_NORMS_PIXELS = 1 << 62
+MAX_STATS_PLANE = 1 << 22        # pixels per plane the exact sums are proved for (include/lgu_corr.h)
+NORM, RES, RES_NORM = 1, 2, 3    # LGU_ENCNORM_NORM, LGU_ENCNORM_RES, LGU_ENCNORM_RES_NORM
+EMIT = 1                         # LGU_ENCNORM_EMIT
+_PRE = {"norm": (NORM, 2), "res": (RES, 3), "res_norm": (RES_NORM, 4)}
 
 STEM = (3, 32)                   # (Cin, Cout) of the 7x7 stride-2 stem
 OUT_CIN, OUT_COUTS = 128, (128, 256)
@@ -158,6 +174,154 @@ def enc_conv3x3(x, pack, stride=1, relu=False, residual=None, down=None):
                                 N, H, W, cin, cout, stride, flags)
         launch("lgu_encconv3x3_h16", "enc_conv3x3", x.device, args, _stream(x))
     return out if down is None else (out, r)
+
+
+def stats_replicas():
+    """R, the slots per plane of an accumulator tensor (lgu_encstats_replicas)."""
+    return int(_lib.load().lgu_encstats_replicas())
+
+
+def new_stats(N, C, device):
+    """Zeroed accumulators (N,C,R,4) int64 for the exact sums of N x C half planes: per plane R = stats_replicas() slots of
+    S1 = sum x 2^24, LO = sum (x 2^24)^2 mod 2^40, HI = sum (x 2^24)^2 >> 40 and BAD = the number of non-finite values
+    (include/lgu_corr.h).  One fill launch."""
+    return torch.zeros((N, C, stats_replicas(), 4), dtype=torch.int64, device=device)
+
+
+def stats_mean_rstd(acc, cnt, eps=1e-5):
+    """(N,C,2) float32 {mean, rstd} of the planes of cnt pixels whose accumulators (N,C,R,4) int64 `acc` holds: the device
+    function the consumer's prologue uses (lgu_encstats_finalize), double arithmetic in the order of include/lgu_corr.h; a
+    plane with BAD != 0 gives NaN for both.  Refusals in this order: acc not (N,C,R,4), not int64, cnt outside
+    [1, 2^22] (above: UnsupportedShape), eps < 0, then contiguity and device."""
+    if acc.dim() != 4 or tuple(acc.shape[2:]) != (stats_replicas(), 4):
+        raise RuntimeError("acc must be (N,C,%d,4), got %s" % (stats_replicas(), tuple(acc.shape)))
+    check_dtype([(acc, "acc")], torch.int64)
+    if cnt < 1:
+        raise RuntimeError("cnt must be >= 1, got %r" % (cnt,))
+    if cnt > MAX_STATS_PLANE:
+        raise _lib.UnsupportedShape("stats_mean_rstd serves planes of at most 2^22 pixels, got %d" % cnt)
+    if not eps >= 0:
+        raise ValueError("eps must be >= 0, got %r" % (eps,))
+    check_contiguous([(acc, "acc")])
+    check_device([(acc, "acc")])
+    out = torch.empty((acc.shape[0], acc.shape[1], 2), dtype=torch.float32, device=acc.device)
+    if out.numel():
+        args = _lib.EncStatsArgs(acc.data_ptr(), out.data_ptr(), acc.shape[0] * acc.shape[1], int(cnt), float(eps))
+        launch("lgu_encstats_finalize", "stats_mean_rstd", acc.device, args, _stream(acc))
+    return out
+
+
+def enc_conv3x3_norm(x, pack, stride=1, down=None, pre=None, keep=False, emit=False, eps=1e-5, stats_out=None):
+    """`enc_conv3x3(h, pack, stride, down=down)` (identity epilogue) of a tensor h that is formed while x is staged, with the
+    exact sums of the outputs on request: one launch, (out, r, kept, out_stats, r_stats) with None where not asked for.
+
+        pre None                   h = x
+        ("norm", sx)               h = half(relu(IN(x; sx)))                         extractor.py:49-50
+        ("res", sx, y)             h = half(relu(float(y) + relu(IN(x; sx))))        :50, :55, no downsample
+        ("res_norm", sx, y, sy)    h = half(relu(IN(y; sy) + relu(IN(x; sx))))       :50-55, with downsample.1
+
+    IN(v; s) = (float(v) - mean) * rstd per plane with (mean, rstd) = stats_mean_rstd(s, H * W, eps) as the launch forms
+    them itself; sx, sy: accumulators (N,Cin,R,4) int64 of x's and y's planes, y (N,Cin,H,W) half.  One rounding to half; the
+    padding is zeros of h.  keep=True (with a prologue): kept = h as a new (N,Cin,H,W) half tensor.  emit=True: the sums of
+    out's planes are added to out_stats (N,Cout,R,4), those of r's to r_stats; stats_out gives the accumulators to add to
+    (a tensor, or with `down` a pair; zero them first with `new_stats`), otherwise new zeroed ones are made.  out and r are
+    bit for bit enc_conv3x3's on h.  pre None without emit is enc_conv3x3 itself.
+
+    Refusals, in this order, all before anything is launched: x not 4-D, stride not 1 or 2, pack not a pair, bias_h not 1-D,
+    (Cin, Cout, stride) not a served shape (UnsupportedShape), the size of wpack, x not half, down with stride 1, down not a
+    pair, the sizes of dpack and dbias_h, the form of pre, keep without pre, eps < 0, the shape then the dtype of sx, y, sy,
+    stats_out without emit, the form of stats_out, the shape then the dtype of its tensors, H * W > 2^22
+    (UnsupportedShape), then contiguity of every operand, the packs' dtype (half), grad and device, in the order x, wpack,
+    bias_h, dpack, dbias_h, sx, y, sy, out_stats, r_stats; then N == 0 returns the empty result and H*W == 0 raises."""
+    if x.dim() != 4:
+        raise RuntimeError("x must be (N,Cin,H,W), got %s" % (tuple(x.shape),))
+    if stride not in (1, 2):
+        raise RuntimeError("stride must be 1 or 2, got %r" % (stride,))
+    if not isinstance(pack, (tuple, list)) or len(pack) != 2:
+        raise RuntimeError("pack must be (wpack, bias_h) of pack_enc3")
+    wpack, bias_h = pack
+    if bias_h.dim() != 1:
+        raise RuntimeError("bias_h must be (Cout,), got %s" % (tuple(bias_h.shape),))
+    N, cin, H, W = x.shape
+    cout = bias_h.shape[0]
+    if (cin, cout, stride) not in SHAPES:
+        raise _lib.UnsupportedShape("enc_conv3x3_norm serves (Cin, Cout, stride) in %s, got (%d, %d, %d)" % (list(SHAPES), cin, cout, stride))
+    if wpack.numel() != 9 * cin * cout:
+        raise RuntimeError("wpack must hold %d halves (pack_enc3, %d -> %d), got %s" % (9 * cin * cout, cin, cout, tuple(wpack.shape)))
+    check_dtype([(x, "x")], torch.float16)
+    packs = [(wpack, "wpack"), (bias_h, "bias_h")]
+    if down is not None:
+        if stride != 2:
+            raise RuntimeError("down (the 1x1 stride-2 branch) needs stride=2")
+        if not isinstance(down, (tuple, list)) or len(down) != 2:
+            raise RuntimeError("down must be (dpack, dbias_h) of pack_enc1")
+        dpack, dbias_h = down
+        if dpack.numel() != cin * cout:
+            raise RuntimeError("dpack must hold %d halves (pack_enc1, %d -> %d), got %s" % (cin * cout, cin, cout, tuple(dpack.shape)))
+        check_shape([(dbias_h, "dbias_h")], (cout,))
+        packs += [(dpack, "dpack"), (dbias_h, "dbias_h")]
+    mode, sx, y, sy = 0, None, None, None
+    if pre is not None:
+        if not isinstance(pre, (tuple, list)) or not pre or pre[0] not in _PRE or len(pre) != _PRE[pre[0]][1]:
+            raise RuntimeError('pre must be None, ("norm", sx), ("res", sx, y) or ("res_norm", sx, y, sy)')
+        mode = _PRE[pre[0]][0]
+        sx, y, sy = (tuple(pre[1:]) + (None, None))[:3]
+    elif keep:
+        raise RuntimeError("keep=True needs a prologue (pre): without one the staged tensor is x")
+    if not eps >= 0:
+        raise ValueError("eps must be >= 0, got %r" % (eps,))
+    R = stats_replicas()
+    rest = []
+    for t, name, shape, dt in ((sx, "sx", (N, cin, R, 4), torch.int64), (y, "y", (N, cin, H, W), torch.float16), (sy, "sy", (N, cin, R, 4), torch.int64)):
+        if t is not None:
+            check_shape([(t, name)], shape)
+            check_dtype([(t, name)], dt)
+            rest.append((t, name))
+    so, sr = None, None
+    if stats_out is not None:
+        if not emit:
+            raise RuntimeError("stats_out needs emit=True")
+        if down is None:
+            if not isinstance(stats_out, torch.Tensor):
+                raise RuntimeError("stats_out must be one accumulator tensor (N,Cout,R,4) without down")
+            so = stats_out
+        else:
+            if not isinstance(stats_out, (tuple, list)) or len(stats_out) != 2:
+                raise RuntimeError("stats_out must be (out_stats, r_stats) with down")
+            so, sr = stats_out
+        for t, name in ((so, "out_stats"), (sr, "r_stats")):
+            if t is not None:
+                check_shape([(t, name)], (N, cout, R, 4))
+                check_dtype([(t, name)], torch.int64)
+                rest.append((t, name))
+    if H * W > MAX_STATS_PLANE:
+        raise _lib.UnsupportedShape("enc_conv3x3_norm serves planes of at most 2^22 pixels, got %d x %d" % (H, W))
+    named = [(x, "x")] + packs + rest
+    check_contiguous(named)
+    check_dtype(packs, torch.float16)
+    check_no_grad("enc_conv3x3_norm", named)
+    check_device(named)
+    if mode == 0 and not emit:
+        got = enc_conv3x3(x, pack, stride=stride, down=down)
+        return (got if down is None else got[0]), (None if down is None else got[1]), None, None, None
+    Ho, Wo = out_size(H, W, stride)
+    out = torch.empty((N, cout, Ho, Wo), dtype=torch.float16, device=x.device)
+    r = torch.empty_like(out) if down is not None else None
+    kept = torch.empty_like(x) if keep else None
+    if emit and so is None:
+        so = new_stats(N, cout, x.device)
+        sr = new_stats(N, cout, x.device) if down is not None else None
+    if N > 0:
+        if H * W == 0:
+            raise RuntimeError("enc_conv3x3_norm: empty frame (H*W = 0)")
+
+        def p(t):
+            return t.data_ptr() if t is not None else None
+        args = _lib.EncConvNormArgs(x.data_ptr(), wpack.data_ptr(), bias_h.data_ptr(), out.data_ptr(), p(down[0]) if down is not None else None,
+                                    p(down[1]) if down is not None else None, p(r), p(y), p(sx), p(sy), p(kept), p(so), p(sr), float(eps),
+                                    N, H, W, cin, cout, stride, mode, EMIT if emit else 0)
+        launch("lgu_encconv3x3_norm_h16", "enc_conv3x3_norm", x.device, args, _stream(x))
+    return out, r, kept, so, sr
 
 
 def shape_of(conv):

@@ -6,7 +6,10 @@ By default the 13 convolutions stay the module's own calls (MIOpen); with `convs
 layer1..3 go through csrc/encconv.hip under float16 autocast (`encconv.enc_conv3x3`, identity epilogue, the 1x1 downsample
 branch of a strided block from its first launch), opt-in because the library's summation order differs and
 `features.install(m)` keeps its bits; with `ends=True` the stem and the output 1x1 go through csrc/encends.hip
-(`encconv.enc_stem7x7`, `encconv.enc_out1x1`), opt-in for the same reason and independent of `convs`.  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
+(`encconv.enc_stem7x7`, `encconv.enc_out1x1`), opt-in for the same reason and independent of `convs`; with `norms=True` (and
+`convs`) 11 of the 13 instance-norm launches fold into the twelve convolutions (`encconv.enc_conv3x3_norm`: exact integer
+statistics from the producer's write-out, the normalisation in the consumer's staging loop), 17 launches per forward with
+`ends`, opt-in because its bits are not `instance_norm_relu`'s.  Everything around them, 15 InstanceNorm2d sites, 13 ReLUs and
 6 residual add + ReLU pairs, becomes one call per site group, 13 per forward: each convolution output is read once, the
 statistics are taken in fp32 from the stored values, and the block output is rounded to the tensor type once.  A call
 is one launch while H*W <= resident_limit(dtype): every site of a 384x512 frame under float16 autocast (13 launches).
@@ -133,6 +136,17 @@ def _check_conv(m, cin, cout, k, stride, pad, name):
                            % (name, cin, cout, k, stride, pad))
 
 
+class _Like:
+    """The shape of a tensor that does not exist yet, for encconv.serves."""
+    __slots__ = ("shape",)
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+    def dim(self):
+        return len(self.shape)
+
+
 class FeatureEncoder:
     """Callable stand-in for the forward of the reference's `BasicEncoder(output_dim, norm_fn='instance')`:
 
@@ -156,10 +170,21 @@ class FeatureEncoder:
     least encconv.MIN_OUT_PIXELS of them (csrc/encends.hip); the instance-norm calls are the same.  Independent of `convs`;
     the fp32 path does not change.  The default, False, keeps both the module's own.
 
+    norms=True (with convs=True): under float16 autocast, where all twelve residual-stage convolutions are served, every
+    plane has at most 2^22 pixels and the call has at least encconv.MIN_NORMS_PIXELS image pixels (N * H * W), the instance
+    norms between the convolutions are folded into them (`encconv.enc_conv3x3_norm`): stem, norm1's call, one fill of the
+    accumulators of the whole forward, twelve convolutions (each but the last adds the exact sums of its outputs; each but
+    the first normalises, adds the residual and applies the ReLUs while it stages its input; the first convolution of a
+    block whose input is a residual later writes it out), the last block's norm call, the output layer: 17 launches with
+    `ends`, counted in `folded_calls`.  The statistics are exact and the normalised value is rounded to half once, so the
+    bits are not those of the per-site route.  Every other call runs the per-site route unchanged.  The default, False,
+    keeps the 13 instance-norm calls.  As measured the folded forward is the slower one at 1 and
+    16 frames of 384x512, so encconv.MIN_NORMS_PIXELS is 1 << 62 and the flag changes nothing until that is lowered.
+
     Construction refuses (RuntimeError naming the attribute) anything but conv1 / norm1 / layer1..3 of two residual
     blocks each / conv2 with InstanceNorm2d(affine=False, track_running_stats=False) at every norm site."""
 
-    def __init__(self, module, convs=False, ends=False):
+    def __init__(self, module, convs=False, ends=False, norms=False):
         conv1 = getattr(module, "conv1", None)
         if not isinstance(conv1, torch.nn.Conv2d):
             raise RuntimeError("FeatureEncoder: conv1 must be a Conv2d")
@@ -203,8 +228,10 @@ class FeatureEncoder:
         self.module = module
         self.convs = bool(convs)
         self.ends = bool(ends)
+        self.norms = bool(norms)
         self._packs = PackCache()
         self.fused_calls = 0
+        self.folded_calls = 0        # calls made by folded forwards, 17 each: one launch each with `ends`
 
     def _convs(self):
         m = self.module
@@ -247,6 +274,10 @@ class FeatureEncoder:
             return None
         y = _instnorm(y, None, y, 0, m.norm1.eps)
         own = self.convs and dt == torch.float16      # the residual stages on csrc/encconv.hip
+        if own and self.norms and self._folds(x4, y):
+            out = self._output(self._folded(y), ends, b, n)
+            self.folded_calls += 17                   # stem, norm1, the fill, twelve convolutions, the last norm, the output layer
+            return out
         for blk in self.blocks:
             r = None
             if own and encconv.serves(blk.conv1, y):
@@ -274,11 +305,71 @@ class FeatureEncoder:
                 if not ok(r):
                     return None
                 y = _instnorm(t, r, t, 2, blk.norm2.eps)
+        return self._output(y, ends, b, n)
+
+    def _output(self, y, ends, b, n):
+        m = self.module
         if ends and encconv.serves_out(m.conv2, y):
             y = encconv.enc_out1x1(y, self._packs.of(m.conv2, encconv.pack_out1))
         else:
             y = m.conv2(y)
         return y.view(b, n, y.shape[1], y.shape[2], y.shape[3])
+
+    def _folds(self, x4, y):
+        """The folded route serves this call: y (N,32,H,W) is norm1's output for the images x4."""
+        if x4.shape[0] * x4.shape[2] * x4.shape[3] < encconv.MIN_NORMS_PIXELS or y.shape[2] * y.shape[3] > encconv.MAX_STATS_PLANE:
+            return False
+        like = _Like(y.shape)
+        for i, blk in enumerate(self.blocks):
+            shape = encconv.shape_of(blk.conv1)
+            if shape is None or (blk.downsample is not None) != (shape[2] == 2) or not encconv.serves(blk.conv1, like):
+                return False
+            if blk.downsample is not None and (i % 2 == 1 or blk.downsample[0].bias is None):
+                return False
+            like = _Like((like.shape[0], shape[1]) + encconv.out_size(like.shape[2], like.shape[3], shape[2]))
+            if not encconv.serves(blk.conv2, like):
+                return False
+        return like.shape[2] * like.shape[3] > 1      # what the last block's norm call needs
+
+    def _folded(self, y):
+        """layer1..3 with the instance norms inside the convolutions, from norm1's output to layer3's: 15 launches."""
+        N, R = y.shape[0], encconv.stats_replicas()
+        packs = self._packs
+        flat = encconv.new_stats(N, self._stat_planes(), y.device).view(-1)
+        taken = [0]
+
+        def site(c):                                  # the accumulators of one convolution's output planes
+            k = N * c * R * 4
+            taken[0] += k
+            return flat[taken[0] - k:taken[0]].view(N, c, R, 4)
+
+        x, pre, resid, eps = y, None, y, 0.0          # resid: the block's input where it exists as a tensor
+        for i, blk in enumerate(self.blocks):
+            last = i == len(self.blocks) - 1
+            cout = blk.conv1.out_channels
+            s1 = site(cout)
+            if blk.downsample is None:
+                t, _, kept, _, _ = encconv.enc_conv3x3_norm(x, packs.of(blk.conv1, encconv.pack_enc3), pre=pre, keep=pre is not None,
+                                                            emit=True, eps=eps, stats_out=s1)
+                resid = kept if pre is not None else resid
+            else:
+                sr = site(cout)
+                t, r, _, _, _ = encconv.enc_conv3x3_norm(x, packs.of(blk.conv1, encconv.pack_enc3), stride=2,
+                                                         down=packs.of(blk.downsample[0], encconv.pack_enc1), pre=pre, emit=True,
+                                                         eps=eps, stats_out=(s1, sr))
+            s2 = None if last else site(cout)
+            t = encconv.enc_conv3x3_norm(t, packs.of(blk.conv2, encconv.pack_enc3), pre=("norm", s1), emit=not last, eps=blk.norm1.eps,
+                                         stats_out=s2)[0]
+            if last:
+                return _instnorm(t, resid, t, 1, blk.norm2.eps)
+            pre = ("res", s2, resid) if blk.downsample is None else ("res_norm", s2, r, sr)
+            x, eps = t, blk.norm2.eps
+
+    def _stat_planes(self):
+        """Planes per image that a folded forward takes statistics of: every convolution output but the last, and the
+        two branches."""
+        total = sum(2 * blk.conv1.out_channels + (blk.conv1.out_channels if blk.downsample is not None else 0) for blk in self.blocks)
+        return total - self.blocks[-1].conv1.out_channels
 
     def __call__(self, x):
         m = self.module
@@ -292,11 +383,11 @@ class FeatureEncoder:
         return out
 
 
-def install(module, convs=False, ends=False):
+def install(module, convs=False, ends=False, norms=False):
     """Bind a FeatureEncoder as `module.forward` (an instance attribute: parameters, buffers and state_dict keys are
-    unchanged), so every caller of the encoder reaches the fused path.  `convs` and `ends` as in FeatureEncoder.  Returns
-    the wrapper; a second call returns the one already installed (with the `convs` and `ends` it was made with)."""
-    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module, convs=convs, ends=ends))
+    unchanged), so every caller of the encoder reaches the fused path.  `convs`, `ends` and `norms` as in FeatureEncoder.
+    Returns the wrapper; a second call returns the one already installed (with the flags it was made with)."""
+    return bind(module, "forward", FeatureEncoder, lambda _: FeatureEncoder(module, convs=convs, ends=ends, norms=norms))
 
 
 def uninstall(module):

@@ -17,6 +17,15 @@ and with --ends the two ends of the encoders (csrc/encends.hip), written to prof
   net_inp                           enc_out1x1(x, split=True)           against conv2(x).split + tanh + relu
   cnet_ends                         ContextEncoder(cnet, ends=True)     against ContextEncoder(cnet)
   fnet_ends                         FeatureEncoder(fnet, convs=True, ends=True)  against FeatureEncoder(fnet, convs=True)
+and with --norms the instance norms folded into the convolutions (enc_conv3x3_norm), written to profiles/encnorm_prof.json,
+each form in ROUNDS = 3 rounds of alternated calls (`rounds`; `keep_fused` must hold in every round):
+  fnet_norms                        FeatureEncoder(fnet, convs=True, ends=True, norms=True)  against the same without norms
+  <Cin>-<Cout>-s<stride>/emit       enc_conv3x3_norm(x, emit=True)                against enc_conv3x3(x) (both with the branch
+  <Cin>-<Cout>-s<stride>/norm       ..(x, pre=("norm", sx))                       where the stride is 2)
+  <Cin>-<Cout>-s<stride>/res        ..(x, pre=("res", sx, y), keep=True)
+  <Cin>-<Cout>-s<stride>/res_norm   ..(x, pre=("res_norm", sx, y, sy), keep=True)
+`min_norms_pixels`: the rule of `thresholds` over fnet_norms' classes in image pixels N * H * W, for encconv.MIN_NORMS_PIXELS.
+`replicas`: R of the library that ran (variant libraries with -DLGU_ES_REPLICAS=1|2|8 under LGU_LIB_PATH give the sweep).
 Each layer form runs at the plane its layer sees in a 384x512 frame (32 channels: 192x256, 64: 96x128, 128: 48x64).
 Method (tools/prof_conv3.py's): every timed call runs on the next of ROT disjoint input sets, the two sides alternate call
 by call in one process, and a spin kernel ahead of the first event keeps the host's enqueue time out of the window.
@@ -26,7 +35,7 @@ every layer form of the shape keeps the fused path, the rule by which lgu_slam_a
 every class keeps it).
 --spin CYCLES lengthens the spin kernel: a whole forward at one frame is 14 to 27 launches whose enqueue outlasts the default
 spin, so its window then holds host time too (a bimodal sample); 2000000 cycles hide it.
-Usage: prof_encconv.py [--ends] [--reps N] [--out PATH] [--forms a,b] [--frames 1,16] [--spin CYCLES]
+Usage: prof_encconv.py [--ends | --norms] [--reps N] [--out PATH] [--forms a,b] [--frames 1,16] [--spin CYCLES]
 """
 import argparse
 import json
@@ -64,6 +73,11 @@ def layer_forms():
 FORMS = layer_forms() + ["cnet", "fnet_convs"]
 END_FORMS = ["stem/relu", "stem/bare", "out128", "out256", "net_inp", "cnet_ends", "fnet_ends"]
 OUT_ENDS = os.path.join(ROOT, "profiles", "encends_prof.json")
+NORM_TAILS = ("emit", "norm", "res", "res_norm")
+NORM_FORMS = ["fnet_norms"] + [sid(s) + "/" + t for s in E.SHAPES for t in NORM_TAILS]
+OUT_NORMS = os.path.join(ROOT, "profiles", "encnorm_prof.json")
+ROUNDS = 3
+FORWARD_SPIN = 2000000     # a whole forward's enqueue outlasts the default spin
 
 
 def stats(ts):
@@ -87,6 +101,10 @@ def sides_of(form, cnet, fnet, fnet_twin, frames):
     if form == "fnet_convs":
         xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
         return lgu_slam_amd.features.FeatureEncoder(fnet_twin, convs=True), lgu_slam_amd.features.FeatureEncoder(fnet), xs
+    if form == "fnet_norms":
+        xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
+        return (lgu_slam_amd.features.FeatureEncoder(fnet_twin, convs=True, ends=True, norms=True),
+                lgu_slam_amd.features.FeatureEncoder(fnet, convs=True, ends=True), xs)
     if form in ("cnet_ends", "fnet_ends"):
         xs = [RF.make_images(100 + i, frames, *FRAME).cuda() for i in range(ROT)]
         if form == "cnet_ends":
@@ -125,6 +143,23 @@ def sides_of(form, cnet, fnet, fnet_twin, frames):
     for _ in range(ROT):
         x = torch.randn((frames, cin, H, W), generator=g) * 2.0
         xs.append(x.clamp_(min=0.0).half().cuda())          # behind a ReLU: exact zeros
+    if tail in NORM_TAILS:
+        dpack = E.pack_enc1(blk.downsample[0].weight, blk.downsample[0].bias) if st == 2 else None
+        bare = lambda x: E.enc_conv3x3(x, pack, stride=st, down=dpack)      # noqa: E731
+        if tail == "emit":
+            so = E.new_stats(frames, cout, "cuda")
+            so = (so, E.new_stats(frames, cout, "cuda")) if st == 2 else so
+            return (lambda x: E.enc_conv3x3_norm(x, pack, stride=st, down=dpack, emit=True, stats_out=so)), bare, xs
+        # the accumulators of each input set, from an emitting launch whose output is its input
+        eye = torch.zeros((cin, cin, 3, 3), device="cuda")
+        eye[torch.arange(cin), torch.arange(cin), 1, 1] = 1.0
+        ident = E.pack_enc3(eye, torch.zeros(cin, device="cuda"))
+        y = (torch.randn((frames, cin, H, W), generator=g) * 2.0).clamp_(min=0.0).half().cuda()
+        sy = E.enc_conv3x3_norm(y, ident, emit=True)[3]
+        sxs = {x.data_ptr(): E.enc_conv3x3_norm(x, ident, emit=True)[3] for x in xs}
+        pre = {"norm": lambda x: ("norm", sxs[x.data_ptr()]), "res": lambda x: ("res", sxs[x.data_ptr()], y),
+               "res_norm": lambda x: ("res_norm", sxs[x.data_ptr()], y, sy)}[tail]
+        return (lambda x: E.enc_conv3x3_norm(x, pack, stride=st, down=dpack, pre=pre(x), keep=tail != "norm")), bare, xs
     if tail == "bare":
         return (lambda x: E.enc_conv3x3(x, pack, stride=st)), conv, xs
     if tail == "relu":
@@ -138,13 +173,13 @@ def sides_of(form, cnet, fnet, fnet_twin, frames):
             (lambda x: (E.enc_conv3x3(x, pack, stride=2, relu=True), down(x))), xs)
 
 
-def timed(fns, xs, reps, warmup=3):
+def timed(fns, xs, reps, warmup=3, spin=None):
     """{side: [ms]}: the sides alternate call by call; call k of a side uses input set k % ROT."""
     ts = {k: [] for k in fns}
     for k in range(warmup + reps):
         for name, fn in fns.items():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda._sleep(SPIN)
+            torch.cuda._sleep(spin or SPIN)
             a.record()
             fn(xs[k % ROT])
             b.record()
@@ -163,13 +198,23 @@ def measure(reps, forms, frames_list):
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
             for form in forms:
                 fused, other, xs = sides_of(form, cnet, fnet, fnet_twin, frames)
-                ts = timed({"fused": fused, "other": other}, xs, reps)
+                folded = form in NORM_FORMS
+                spin = max(SPIN, FORWARD_SPIN) if form == "fnet_norms" else None
+                rounds = []
+                for _ in range(ROUNDS if folded else 1):
+                    ts = timed({"fused": fused, "other": other}, xs, reps, spin=spin)
+                    f, o = stats(ts["fused"]), stats(ts["other"])
+                    rounds.append({"fused": f, "other": o, "speedup": o["median_ms"] / f["median_ms"],
+                                   "keep_fused": bool(f["median_ms"] + f["spread_ms"] < o["median_ms"] - o["spread_ms"])})
                 del xs
                 torch.cuda.empty_cache()
-                f, o = stats(ts["fused"]), stats(ts["other"])
-                d = {"fused": f, "other": o, "speedup": o["median_ms"] / f["median_ms"],
-                     "keep_fused": bool(f["median_ms"] + f["spread_ms"] < o["median_ms"] - o["spread_ms"])}
-                if form.startswith("stem/"):
+                d = dict(rounds[len(rounds) // 2])
+                if folded:     # the middle round's figures, every round listed, and the verdict of all of them
+                    d["rounds"] = rounds
+                    d["keep_fused"] = all(r["keep_fused"] for r in rounds)
+                if form == "fnet_norms":
+                    d["out_pixels"] = frames * FRAME[0] * FRAME[1]
+                elif form.startswith("stem/"):
                     ho, wo = E.out_size(*FRAME, 2)
                     d["out_pixels"] = frames * ho * wo
                 elif form in ("out128", "out256", "net_inp"):
@@ -222,6 +267,8 @@ def main():
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--ends", action="store_true", help="time the stem and the output layer (csrc/encends.hip) instead: "
                     "profiles/encends_prof.json")
+    ap.add_argument("--norms", action="store_true", help="time the folded instance norms (enc_conv3x3_norm, FeatureEncoder(norms=True)) "
+                    "instead: profiles/encnorm_prof.json")
     ap.add_argument("--out")
     ap.add_argument("--forms", help="comma-separated subset of the forms to time (e.g. a variant library under LGU_LIB_PATH); "
                     "no thresholds are derived from a subset")
@@ -232,12 +279,17 @@ def main():
     lgu_slam_amd._lib.load()
     E.MIN_FUSED_PIXELS = {s: 0 for s in E.SHAPES}      # measure the fused path at every class; the rule is applied afterwards
     E.MIN_STEM_PIXELS, E.MIN_OUT_PIXELS = 0, {c: 0 for c in E.OUT_COUTS}
-    args.out = args.out or (OUT_ENDS if args.ends else OUT)
-    forms = args.forms.split(",") if args.forms else list(END_FORMS if args.ends else FORMS)
+    E.MIN_NORMS_PIXELS = 0
+    args.out = args.out or (OUT_NORMS if args.norms else OUT_ENDS if args.ends else OUT)
+    forms = args.forms.split(",") if args.forms else list(NORM_FORMS if args.norms else END_FORMS if args.ends else FORMS)
     workloads = measure(args.reps, forms, [int(f) for f in args.frames.split(",")])
     doc = {"tool": "prof_encconv", "device": torch.cuda.get_device_name(0), "lib": lgu_slam_amd._lib.version(),
            "reps": args.reps, "rotation": ROT, "spin_cycles": args.spin, "workloads": workloads}
-    if not args.forms and args.ends:
+    if args.norms:
+        doc["replicas"] = E.stats_replicas()
+        if "fnet_norms" in forms:
+            doc["min_norms_pixels"] = threshold_of(workloads, ("fnet_norms",))
+    elif not args.forms and args.ends:
         doc["min_stem_pixels"] = threshold_of(workloads, ("stem/relu", "stem/bare"))
         doc["min_out_pixels"] = {"128": threshold_of(workloads, ("out128",)), "256": threshold_of(workloads, ("out256", "net_inp"))}
     elif not args.forms:
