@@ -1203,6 +1203,55 @@ typedef struct {
 int lgu_encstats_finalize(lgu_encstats_args args, void* stream);
 int lgu_encstats_replicas(void);
 
+/* ---- the Gaussian mask's parameter head: Linear(256, 16) + Tanh, then Linear(16, 2) twice, in one launch
+ * (csrc/gausshead.hip).  Reference droid_slam/gaussianMask_cuda.py:69-73: tt = mapA(x), meanMap(tt), covMap(tt); what follows
+ * them (:74-83) is lgu_gaussian_params.  x (E,H,W,256) channel-last contiguous; mean_ofs (E,H,W,2), cov_raw (E,H*W,2) and,
+ * where the pointer is not null, hidden (E,H,W,16) = tt: fully written, nothing outside them; they overlap neither x nor
+ * one another.  Per pixel p, with W2 = [Wm; Wc] (4,16) and b2 = [bm; bc] (4):
+ *   half mode (flags without LGU_GAUSSHEAD_FP32): what float16 autocast evaluates.  x float32, or IEEE half with
+ *   LGU_GAUSSHEAD_X_HALF; parameters and outputs IEEE half.  Rounding points:
+ *     x_h = half(x), W_h = half(W), b_h = half(b)           round to nearest even (x_h in the load, a half x is used as it
+ *                                                           is; the parameters in the pack)
+ *     s1  = sum over c of x_h[p][c] * W1_h[k][c]            exact products, fp32 accumulation from zero in a fixed order (8
+ *                                                           steps of 32 channels, ascending)
+ *     u   = half(b1_h[k] + s1)                              one fp32 addition, ONE rounding
+ *     tt  = half(tanhf(float(u)))                           the device library's float tanh, ONE rounding; NaN is kept
+ *     s2  = sum over k of tt[k] * W2_h[o][k]                exact products, fp32 accumulation from zero (one step of 16)
+ *     out = half(b2_h[o] + s2)                              one fp32 addition, ONE rounding; o = 0,1: mean_ofs, 2,3: cov_raw
+ *   fp32 mode (LGU_GAUSSHEAD_FP32; not with LGU_GAUSSHEAD_X_HALF): x, parameters and outputs float32, no half rounding:
+ *     s1  = fp32 fused multiply-add chains on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, one rounding per term): the
+ *           channels 16 m + 4 g + i in the order g, i, m for even m and for odd m, the two chains added once
+ *     tt  = tanhf(b1[k] + s1),  out = b2[o] + (the chain over k = 0..15)
+ * The bits of a pixel depend on its own 256 inputs only: not on E, the pixel's position, its tile or the launch geometry.
+ * A NaN or infinite input reaches exactly its own pixel's 4 outputs and 16 hidden values.  No atomics, no workspace, no
+ * LDS, no host synchronisation.
+ * wpack: LGU_GAUSSHEAD_WPACK_ELEMS = 256 * 16 + 64 * 4 elements (half, or float32 in fp32 mode), bias: LGU_GAUSSHEAD_BIAS_ELEMS
+ *   = 20 elements of the same type, [b1 (16); bm (2); bc (2)].  With lane l, r = l & 15, g = l >> 4:
+ *   half: wpack[(kc * 64 + l) * 8 + j] = W1_h[r][32 kc + 8 g + j] (kc < 8, j < 8): the A operand of v_mfma_f32_16x16x32_f16;
+ *         wpack[4096 + 4 l + j] = W2_h[r][4 g + j] for r < 4 and ZERO for r >= 4 (j < 4): the A operand of
+ *         v_mfma_f32_16x16x16_f16.
+ *   fp32: wpack[s * 64 + l] = W1[r][16 (s >> 2) + 4 g + (s & 3)] (s < 64); wpack[4096 + 64 i + l] = W2[r][4 g + i] for r < 4
+ *         and ZERO for r >= 4 (i < 4): the A operands of v_mfma_f32_16x16x4_f32, one K step each.
+ * x and wpack must be 16-byte aligned, otherwise LGU_E_UNSUPPORTED; bias and the outputs are served at the alignment of
+ * their element with the same bits (they are accessed by element).
+ * The layer sizes are fixed (256 in, 16 hidden, 2 + 2 out: LGU_GAUSSHEAD_CIN, LGU_GAUSSHEAD_HIDDEN) and the block
+ * carries no size: the Python layer refuses any other layer before it gets here.  E, H or W < 0, an unknown flag or both
+ * flags: LGU_E_BADARG; E, H or W == 0: LGU_OK, nothing launched; a null x, wpack, bias, mean_ofs or cov_raw, or bias or an
+ * output below its element's alignment: LGU_E_BADARG; more than INT_MAX - 16 pixels: LGU_E_UNSUPPORTED.  Every refusal comes
+ * before any launch and writes nothing.  The operands travel in one parameter block passed by value. */
+#define LGU_GAUSSHEAD_CIN 256
+#define LGU_GAUSSHEAD_HIDDEN 16
+#define LGU_GAUSSHEAD_WPACK_ELEMS 4352
+#define LGU_GAUSSHEAD_BIAS_ELEMS 20
+#define LGU_GAUSSHEAD_X_HALF 1   /* flags: x holds IEEE half (half mode only) */
+#define LGU_GAUSSHEAD_FP32 2     /* flags: fp32 mode */
+typedef struct {
+  const void* x; const void* wpack; const void* bias;
+  void* mean_ofs; void* cov_raw; void* hidden;              /* hidden: or null */
+  int E, H, W, flags;
+} lgu_gausshead_args;
+int lgu_gaussian_head(lgu_gausshead_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

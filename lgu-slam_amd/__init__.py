@@ -20,7 +20,8 @@ from .encconv import enc_conv3x3, enc_conv3x3_norm, enc_out1x1, enc_stem7x7, pac
 from .encoder import CorrEncoder  # noqa: F401
 from .features import FeatureEncoder  # noqa: F401
 from .flow import FlowEncoder  # noqa: F401
-from .gaussian_mask import GaussianMask, GaussianMaskCuda  # noqa: F401
+from . import gaussian_mask  # noqa: F401
+from .gaussian_mask import GaussianHead, GaussianMask, GaussianMaskCuda, gaussian_head, pack_gaussian_head  # noqa: F401
 from .gru import KanBiasGRU, gru_conv3x3, gru_conv_q, gru_conv_zr, pack_gruconv  # noqa: F401
 from .heads import Head, head_pair  # noqa: F401
 from .upmask import Upmask  # noqa: F401

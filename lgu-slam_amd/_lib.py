@@ -97,6 +97,12 @@ class EncOutArgs(ctypes.Structure):
                 ("Cin", _int), ("Cout", _int), ("flags", _int)]
 
 
+class GaussHeadArgs(ctypes.Structure):
+    """lgu_gausshead_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("x", _vp), ("wpack", _vp), ("bias", _vp), ("mean_ofs", _vp), ("cov_raw", _vp), ("hidden", _vp), ("E", _int),
+                ("H", _int), ("W", _int), ("flags", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -240,6 +246,9 @@ SIGNATURES = {
     # the encoders' output 1x1, 128 -> 128 | 256, with the tanh / relu split: {x, wpack, bias, out, inp, N, H, W, Cin, Cout,
     # flags} by value, stream
     "lgu_encout1x1_c128_h16": [EncOutArgs, _vp],
+    # the Gaussian mask's parameter head, Linear(256,16) + tanh + 2 x Linear(16,2): {x, wpack, bias, mean_ofs, cov_raw, hidden,
+    # E, H, W, flags} by value, stream
+    "lgu_gaussian_head": [GaussHeadArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],
