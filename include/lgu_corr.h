@@ -1252,6 +1252,49 @@ typedef struct {
 } lgu_gausshead_args;
 int lgu_gaussian_head(lgu_gausshead_args args, void* stream);
 
+/* ---- the map export: the filtered, coloured point cloud of a set of keyframes, compacted on the device (csrc/cloud.hip).
+ * Reference droid_slam/visualization.py:92-129: iproj under the inverted poses, depth_filter, the per-frame disparity floor
+ * and the boolean index per frame.  poses (np,7), disps (nd,ht,wd), intrinsics, ix (num) int64 and thresh (num) as the
+ * geometry entries above take them; floor (num) float: the per-entry disparity floor.  For entry b and pixel k (row-major)
+ * of frame ix[b]:
+ *   count = what lgu_depth_filter_f32 writes for that pixel (one shared definition, csrc/geom_pixel.hpp; an ix[b] outside
+ *           [0, min(np, nd)) counts 0)
+ *   keep  = count >= min_count && disps[ix[b]][k] > floor[b]        (float comparison; an invalid ix[b] keeps nothing,
+ *           whatever min_count)
+ *   point = what lgu_iproj_f32 writes for that pixel (the same shared definition) under the inverse of poses[ix[b]], the
+ *           inverse formed once per workgroup as conj(q), uv = 2 (v x t), w = v x uv, -((t + q.w uv) + w) with every product
+ *           and sum rounded on its own, except a cross product's a1 b2 - a2 b1 = fma(a1, b2, -(a2 b1)), as the framework's
+ *           cross product evaluates it: the bits of the pure-framework inverse the callers of lgu_iproj_f32 use
+ *   colour[c] = float(images[ix[b]][2 - c][phase + stride i][phase + stride j]) * r255 with lgu_image_normalize_u8's r255,
+ *           or with color_u8 the byte itself; images (ni,3,H,W) uint8 BGR, or null: no colours
+ * Kept pixels are written densely, entries in ix order and pixels ascending inside an entry: entry b owns the rows
+ * offsets[b] : offsets[b + 1] of points (cap,3) float and colors (cap,3) float or uint8.  A row >= cap is not written;
+ * offsets (num + 1) int64 always holds the true totals.  The order comes from the launch boundaries (no atomics, no
+ * workgroup waits on another): the same bits on every run.
+ *
+ * lgu_cloud_decide_f32   two launches: count, keep and the 64-lane ballot words of keep into scratch; then one workgroup forms
+ *   the exclusive prefix of the kept counts and writes offsets.  Reads poses .. floor, min_count; writes scratch, offsets.
+ * lgu_cloud_write_f32    one launch: every kept lane ranks itself from the ballot words and the prefix in scratch and stores its
+ *   point and colour.  Takes the scratch of a lgu_cloud_decide_f32 call with the same num, ht, wd, ix; reads poses, disps,
+ *   intrinsics, ix, images; writes points and colors below cap.  cap == 0: nothing is launched.
+ * scratch: lgu_cloud_scratch_bytes(num, ht, wd) bytes of device memory, 8-byte aligned like offsets (else LGU_E_BADARG); it
+ * needs no initialisation.  Sizes as the geometry entries' (num == 0 or an empty frame: nothing is launched; more than
+ * 65535 * 256 pixels per frame: LGU_E_UNSUPPORTED).  With images: ni >= min(np, nd), stride >= 1, phase >= 0, phase + stride
+ * (ht - 1) < H and phase + stride (wd - 1) < W, else LGU_E_BADARG.  Launched on `stream`, no host synchronisation.  The
+ * operands travel in one parameter block passed by value. */
+typedef struct {
+  const float* poses; const float* disps; const float* intrinsics;
+  const long long* ix; const float* thresh; const float* floor;        /* thresh, floor: the decision pass only */
+  const void* images;                                                  /* or null */
+  void* scratch; long long* offsets;                                   /* offsets: the decision pass only */
+  float* points; void* colors; long long cap;                          /* the write pass only; colors: or null */
+  int np, nd, ht, wd, num, min_count;
+  int ni, H, W, stride, phase, color_u8;
+} lgu_cloud_args;
+long long lgu_cloud_scratch_bytes(int num, int ht, int wd);
+int lgu_cloud_decide_f32(lgu_cloud_args args, void* stream);
+int lgu_cloud_write_f32(lgu_cloud_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

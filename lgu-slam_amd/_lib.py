@@ -103,6 +103,14 @@ class GaussHeadArgs(ctypes.Structure):
                 ("H", _int), ("W", _int), ("flags", _int)]
 
 
+class CloudArgs(ctypes.Structure):
+    """lgu_cloud_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("poses", _vp), ("disps", _vp), ("intrinsics", _vp), ("ix", _vp), ("thresh", _vp), ("floor", _vp), ("images", _vp),
+                ("scratch", _vp), ("offsets", _vp), ("points", _vp), ("colors", _vp), ("cap", ctypes.c_longlong), ("np", _int),
+                ("nd", _int), ("ht", _int), ("wd", _int), ("num", _int), ("min_count", _int), ("ni", _int), ("H", _int), ("W", _int),
+                ("stride", _int), ("phase", _int), ("color_u8", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -249,9 +257,14 @@ SIGNATURES = {
     # the Gaussian mask's parameter head, Linear(256,16) + tanh + 2 x Linear(16,2): {x, wpack, bias, mean_ofs, cov_raw, hidden,
     # E, H, W, flags} by value, stream
     "lgu_gaussian_head": [GaussHeadArgs, _vp],
+    # the map export: {poses, disps, intrinsics, ix, thresh, floor, images, scratch, offsets, points, colors, cap, np, nd, ht,
+    # wd, num, min_count, ni, H, W, stride, phase, color_u8} by value, stream
+    "lgu_cloud_decide_f32": [CloudArgs, _vp],
+    "lgu_cloud_write_f32": [CloudArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],
+    "lgu_cloud_scratch_bytes": [_int] * 3,
     "lgu_proximity_prefix_len": [_int] * 4,
     "lgu_proximity_capacity": [_int] * 5 + [ctypes.c_longlong],
     "lgu_proximity_work_bytes": [_int] * 3,
@@ -261,7 +274,7 @@ SIGNATURES = {
 }
 RESTYPES = {name: ctypes.c_longlong for name in (
     "lgu_ba_solve_blocked_work_doubles", "lgu_offsets_finalize_scratch_bytes", "lgu_proximity_prefix_len", "lgu_proximity_capacity",
-    "lgu_proximity_work_bytes")}
+    "lgu_proximity_work_bytes", "lgu_cloud_scratch_bytes")}
 RESTYPES.update(lgu_instnorm_resident_limit=ctypes.c_long, lgu_version=ctypes.c_char_p, lgu_error_string=ctypes.c_char_p)
 
 _lib = None

@@ -4,37 +4,24 @@
 // Per-pixel arithmetic is the reference's, in its fp32 operation order (built with -ffp-contract=off; fp32 `/` and
 // sqrtf are correctly rounded), so every per-pixel value is bit-identical to a float32 restatement of the reference
 // (tests/geom_restatement.py).  Only frame_distance's three sums are ordered differently (fixed order, see below).
+// The count of depth_filter and the point of iproj are defined in geom_pixel.hpp, which the map export (cloud.hip) shares.
 //
 // Index rule (the reference reads out of bounds instead): a frame index is valid when 0 <= index < nvalid =
 // min(rows of poses, frames of disps).  No kernel dereferences an invalid index; it writes NaN (frame_distance), NaN
 // coordinates with channel 2 = 0 and valid = 0 (projmap), a zero row (depth_filter: an invalid ix; an invalid
 // neighbour is skipped like the reference's out-of-buffer ones), NaN points (iproj: a frame without a pose).
-#include <limits.h>
-
 #include "lgu_common.hpp"
-#include "se3.hpp"
+#include "geom_pixel.hpp"
 
 namespace lgu {
 
 constexpr float GEOM_MIN_DEPTH = 0.25f;  // droid_kernels.cu:26 (0.25 is exact in float: same comparisons)
-constexpr int GEOM_THREADS = 256;
 constexpr int FD_MAX_WAVES = 16;
 constexpr int FD_LANE_PIXELS = 8;        // target pixels per lane of frame_distance
 
 __device__ __forceinline__ float readlane_f32(float v, int lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
 }
-
-// static_cast<int>(floor(x)) as the hardware conversion (v_cvt_i32_f32) performs it, which is what the reference gets on
-// every vendor: NaN -> 0, values outside the int range saturate.  Written out so that no input is undefined behaviour.
-__device__ __forceinline__ int cvt_i32_sat(float f) {
-  if (f != f) return 0;
-  if (f >= 2147483648.0f) return INT_MAX;
-  if (f < -2147483648.0f) return INT_MIN;
-  return (int)f;
-}
-
-__device__ __forceinline__ bool valid_index(long long v, int nvalid) { return v >= 0 && v < nvalid; }
 
 // ---- frame_distance (:518-658) --------------------------------------------------------------------------------------
 // One workgroup per pair, nw = blockDim.x / 64 waves.  Wave w owns the rows [w * rpw, (w + 1) * rpw), lane l the
@@ -209,47 +196,12 @@ __global__ __launch_bounds__(GEOM_THREADS) void depth_filter_kernel(
     return;
   }
   const int ix = (int)a;
-  if (threadIdx.x < 6) {
-    const int n = threadIdx.x;
-    const long long jx = n < 3 ? a - n - 1 : a + n;
-    if (valid_index(jx, nvalid)) {
-      rel_se3(poses + ix * 7, poses + ix * 7 + 3, poses + jx * 7, poses + jx * 7 + 3, rel[n], rel[n] + 3);
-      nbr[n] = (int)jx;
-    } else {
-      nbr[n] = -1;
-    }
-  }
+  if (threadIdx.x < DF_NEIGHBOURS) depth_filter_neighbour(poses, a, threadIdx.x, nvalid, rel[threadIdx.x], &nbr[threadIdx.x]);
   __syncthreads();
   if (k >= HW) return;
   const float fx = intrinsics[0], fy = intrinsics[1], cx = intrinsics[2], cy = intrinsics[3];
-  const double t = (double)thresh[b];
   const int i = k / wd, j = k - i * wd;
-  const float ui = static_cast<float>(j), vi = static_cast<float>(i);
-  const float di = disps[(size_t)ix * HW + k];
-  const float X[3] = {(ui - cx) / fx, (vi - cy) / fy, 1.0f};
-  int cnt = 0;
-  for (int n = 0; n < 6; n++) {
-    const int jx = nbr[n];
-    if (jx < 0) continue;  // uniform
-    const float* R = rel[n];
-    float Y[3];
-    act_so3(R + 3, X, Y);
-    Y[0] += di * R[0];
-    Y[1] += di * R[1];
-    Y[2] += di * R[2];
-    const float uj = fx * (Y[0] / Y[2]) + cx;
-    const float vj = fy * (Y[1] / Y[2]) + cy;
-    const float dj = di / Y[2];
-    const int u0 = cvt_i32_sat(floorf(uj)), v0 = cvt_i32_sat(floorf(vj));
-    if (u0 >= 0 && v0 >= 0 && u0 < wd - 1 && v0 < ht - 1) {
-      const float* Dj = disps + (size_t)jx * HW + (size_t)v0 * wd + u0;
-      const float d00 = Dj[0], d01 = Dj[1], d10 = Dj[wd], d11 = Dj[wd + 1];
-      const double r = 1.0 / (double)dj;
-      if (fabs(r - 1.0 / (double)d00) < t || fabs(r - 1.0 / (double)d01) < t || fabs(r - 1.0 / (double)d10) < t ||
-          fabs(r - 1.0 / (double)d11) < t)
-        cnt++;
-    }
-  }
+  const int cnt = depth_filter_count(disps, fx, fy, cx, cy, (double)thresh[b], rel, nbr, disps[(size_t)ix * HW + k], i, j, ht, wd);
   counter[(size_t)b * HW + k] = (float)cnt;
 }
 
@@ -268,26 +220,13 @@ __global__ __launch_bounds__(GEOM_THREADS) void iproj_kernel(
     return;
   }
   const float fx = intrinsics[0], fy = intrinsics[1], cx = intrinsics[2], cy = intrinsics[3];
-  const float* t = poses + (size_t)n * 7;
   const int i = k / wd, j = k - i * wd;
-  const float ui = static_cast<float>(j), vi = static_cast<float>(i);
-  const float di = disps[(size_t)n * HW + k];
-  const float X[3] = {(ui - cx) / fx, (vi - cy) / fy, 1.0f};
-  float Y[3];
-  act_so3(t + 3, X, Y);
-  Y[0] += di * t[0];
-  Y[1] += di * t[1];
-  Y[2] += di * t[2];
-  P[0] = Y[0] / di;
-  P[1] = Y[1] / di;
-  P[2] = Y[2] / di;
+  float Q[3];
+  iproj_point(poses + (size_t)n * 7, fx, fy, cx, cy, disps[(size_t)n * HW + k], i, j, Q);
+  P[0] = Q[0];
+  P[1] = Q[1];
+  P[2] = Q[2];
 }
-
-inline bool geom_dims_ok(int np, int nd, int ht, int wd) {
-  return np >= 0 && nd >= 0 && ht >= 0 && wd >= 0 && (long long)ht * wd <= (long long)INT_MAX / 3;
-}
-
-inline int pixel_blocks(int ht, int wd) { return (ht * wd + GEOM_THREADS - 1) / GEOM_THREADS; }
 
 }  // namespace lgu
 
