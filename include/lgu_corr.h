@@ -1295,6 +1295,58 @@ long long lgu_cloud_scratch_bytes(int num, int ht, int wd);
 int lgu_cloud_decide_f32(lgu_cloud_args args, void* stream);
 int lgu_cloud_write_f32(lgu_cloud_args args, void* stream);
 
+/* ---- the frame intake: rectify, resize, crop and normalise a decoded camera frame in one launch (csrc/intake.hip).
+ * What the reference's streams do on the host before Droid.track (demo.py:39-54, demo_depth.py:39-65,
+ * evaluation_scripts/test_tum.py:34-52, test_euroc.py:29-76) and motion_filter.py:56-57 after it.  The definition is
+ * tests/intake_restatement.py; DESIGN.md section 3.26 states it in full.
+ *   raw (N,h0,w0,C) uint8, C = 3 (BGR, interleaved as decoders deliver it) or 1 (grey, replicated)
+ *   stage 1, present when ncam > 0: pixel (u,v) of the rectified image (h0,w0) reads raw at the camera's map, in double
+ *     with every operation rounded on its own (no contraction): x = (u - kn[2]) / kn[0], y = (v - kn[3]) / kn[1];
+ *     (X,Y,W) = ((ir[3r] x + ir[3r+1] y) + ir[3r+2]); x = X / W, y = Y / W; r2 = x x + y y;
+ *     rad = 1 + r2 (d[0] + r2 (d[1] + r2 d[4])); t = 2 (x y); xd = (x rad + d[2] t) + d[3] (r2 + 2 (x x));
+ *     yd = (y rad + d[2] (r2 + 2 (y y))) + d[3] t; m = (xd k[0] + k[2], yd k[1] + k[3]).  q = floor(32 m + 0.5) per axis,
+ *     clamped to [-2^30, 2^30] (a NaN to -2^30); taps (q >> 5, (q >> 5) + 1) with weights (32 - (q & 31), q & 31), a tap
+ *     outside the raw frame contributes 0; byte = (sum + 512) >> 10 per channel
+ *   stage 2, present when (h1,w1) != (h0,w0): per axis f = (o + 0.5) (n_in / n_out) - 0.5 in double, i0 = floor(f),
+ *     a = f - i0; i0 < 0: i0 = 0, a = 0; i0 >= n_in - 1: i0 = n_in - 1, a = 0; i1 = min(i0 + 1, n_in - 1);
+ *     k = floor(2048 a + 0.5); byte = (sum of the four stage-1 BYTES with weights (2048 - k, k) per axis + 2^21) >> 22
+ *   stage 3: the rectangle (top, left, H, W) of the (h1,w1) image
+ *   image (N,3,H,W) uint8 BGR planar; inputs (N,3,H,W) float RGB or null: lgu_image_normalize_u8's value of image, the
+ *     same device function (csrc/image_norm.hpp), with mean[3], std[3] RGB
+ * Cameras: ncam = 0 (no stage 1), 1 (shared by the batch) or N (one per frame).  Up to 2 travel in the block (cam);
+ * more as a device table cam_table (ncam entries, 8-byte aligned), else LGU_E_BADARG.  lgu_intake_camera is 22 doubles:
+ * k = fx, fy, cx, cy of the raw camera; kn = the same of the rectified camera; ir = the inverse of the rectifying
+ * rotation, row-major; d = k1, k2, p1, p2, k3.
+ * path: 0 picks the kernel (the LDS tile when both stages are present and the tile's stage-1 rectangle fits, else the
+ * direct kernel); 1 asks for the tile kernel (a workgroup whose rectangle does not fit computes directly), 2 for the
+ * direct kernel.  The bytes do not depend on it.
+ * Negative sizes, C not 1 or 3, a crop outside (h1,w1), an empty raw frame behind a non-empty output, ncam not 0 | 1 | N,
+ * a null raw or image, an unknown path: LGU_E_BADARG.  N == 0 or H W == 0 launches nothing.  More than 65535 frames or
+ * tile rows: LGU_E_UNSUPPORTED.  No atomics; the same bits on every run.  Operands at element alignment.
+ *
+ * lgu_intake_depth_f32  the sensor disparity of depth_video.py:64-66 from the raw depth image: for the points [3::8, 3::8]
+ * of the (top, left, H, W) rectangle of the depth resized to (h1,w1) as the framework's bilinear interpolation without
+ * aligned corners does (f = max((o + 0.5) (n_in / n_out) - 0.5, 0), i0 = floor(f), i1 = i0 + (i0 < n_in - 1), l1 = f - i0,
+ * l0 = 1 - l1): d = ly0 (lx0 p00 + lx1 p01) + ly1 (lx0 p10 + lx1 p11) with p = double(raw) * scale, in double;
+ * out = float(d > 0 ? 1 / d : d).  raw (N,h0,w0) uint16 (src_u16) or float; out (N, (H + 4) / 8, (W + 4) / 8) float.
+ * Refusals as above (an empty raw behind a non-empty output, a crop outside: LGU_E_BADARG). */
+typedef struct {
+  double k[4]; double kn[4]; double ir[9]; double d[5];
+} lgu_intake_camera;
+typedef struct {
+  const void* raw; void* image; float* inputs;                         /* inputs: or null */
+  const lgu_intake_camera* cam_table;                                  /* ncam > 2 only */
+  lgu_intake_camera cam[2];
+  float mean[3]; float std[3];
+  int N, h0, w0, C, h1, w1, top, left, H, W, ncam, path;
+} lgu_intake_args;
+typedef struct {
+  const void* raw; float* out; double scale;
+  int N, h0, w0, h1, w1, top, left, H, W, src_u16;
+} lgu_intake_depth_args;
+int lgu_intake_frame_u8(lgu_intake_args args, void* stream);
+int lgu_intake_depth_f32(lgu_intake_depth_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,24 @@ class CloudArgs(ctypes.Structure):
                 ("stride", _int), ("phase", _int), ("color_u8", _int)]
 
 
+class IntakeCamera(ctypes.Structure):
+    """lgu_intake_camera of include/lgu_corr.h: 22 doubles."""
+    _fields_ = [("k", ctypes.c_double * 4), ("kn", ctypes.c_double * 4), ("ir", ctypes.c_double * 9), ("d", ctypes.c_double * 5)]
+
+
+class IntakeArgs(ctypes.Structure):
+    """lgu_intake_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("raw", _vp), ("image", _vp), ("inputs", _vp), ("cam_table", _vp), ("cam", IntakeCamera * 2),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3), ("N", _int), ("h0", _int), ("w0", _int), ("C", _int),
+                ("h1", _int), ("w1", _int), ("top", _int), ("left", _int), ("H", _int), ("W", _int), ("ncam", _int), ("path", _int)]
+
+
+class IntakeDepthArgs(ctypes.Structure):
+    """lgu_intake_depth_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("raw", _vp), ("out", _vp), ("scale", ctypes.c_double), ("N", _int), ("h0", _int), ("w0", _int), ("h1", _int),
+                ("w1", _int), ("top", _int), ("left", _int), ("H", _int), ("W", _int), ("src_u16", _int)]
+
+
 # name -> argument types; the return type is int unless RESTYPES names another
 SIGNATURES = {
     "lgu_defcorr_fwd_f32": [_vp, _vp, _vp, _vp] + [_int] * 6 + [_vp],
@@ -261,6 +279,10 @@ SIGNATURES = {
     # wd, num, min_count, ni, H, W, stride, phase, color_u8} by value, stream
     "lgu_cloud_decide_f32": [CloudArgs, _vp],
     "lgu_cloud_write_f32": [CloudArgs, _vp],
+    # the frame intake: {raw, image, inputs, cam_table, cam[2], mean[3], std[3], N, h0, w0, C, h1, w1, top, left, H, W, ncam,
+    # path} by value, stream; {raw, out, scale, N, h0, w0, h1, w1, top, left, H, W, src_u16} by value, stream
+    "lgu_intake_frame_u8": [IntakeArgs, _vp],
+    "lgu_intake_depth_f32": [IntakeDepthArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],

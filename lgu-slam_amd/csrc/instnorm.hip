@@ -37,6 +37,7 @@
 #include <limits.h>
 
 #include "lgu_common.hpp"
+#include "image_norm.hpp"
 
 namespace lgu {
 
@@ -388,11 +389,8 @@ struct Rgb {
   float v[3];
 };
 
-// out[n, c, i] = (float(img[n, 2 - c, i]) * IMG_INV255 - mean[c]) / std[c]; one thread per XV consecutive pixels of one
-// output channel.  The product is what the reference's `/ 255.0` is on the device: a tensor divided by a Python number
-// is multiplied by the reciprocal, formed in double and rounded to fp32 once (it equals the correctly rounded quotient
-// for 130 of the 256 byte values only).  The subtraction and the division by std are the tensor-tensor ops: IEEE.
-constexpr float IMG_INV255 = (float)(1.0 / 255.0);
+// out[n, c, i] = image_normalize_value(img[n, 2 - c, i], mean[c], std[c]) (image_norm.hpp: (float(px) * IMG_INV255 - mean)
+// / std); one thread per XV consecutive pixels of one output channel.
 
 template <int XV>
 __global__ __launch_bounds__(IMG_THREADS) void image_normalize_kernel(const unsigned char* __restrict__ img,
@@ -411,10 +409,10 @@ __global__ __launch_bounds__(IMG_THREADS) void image_normalize_kernel(const unsi
     const u8x4 px = *reinterpret_cast<const u8x4*>(img + src);
     f32x4 r;
 #pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = ((float)px[k] * IMG_INV255 - m) / sd;
+    for (int k = 0; k < 4; k++) r[k] = image_normalize_value(px[k], m, sd);
     *reinterpret_cast<f32x4*>(out + dst) = r;
   } else {
-    out[dst] = ((float)img[src] * IMG_INV255 - m) / sd;
+    out[dst] = image_normalize_value(img[src], m, sd);
   }
 }
 
