@@ -45,8 +45,10 @@ def install_dropins(experimental_ba=False, torch_scatter=False, lietorch=False):
     the caller's.
 
     experimental_ba=True additionally binds `droid_backends.ba` to this build's device-side bundle adjustment
-    (lgu_slam_amd.ba.ba) — a first version whose parity with the reference is unpinned (the reference BA needs Eigen
-    and cannot be built here); by default that name raises, like the out-of-scope corr_index_* entries.
+    (lgu_slam_amd.ba.ba) — a first version, held to the reference's own Python BA at lm = 0 (tests/test_ba_reference.py)
+    and, for the damping with lm != 0 that `ba_cuda` applies its own way, to a restatement of `ba_cuda` (the reference's
+    host driver needs Eigen and cannot be built here); by default that name raises, like the out-of-scope corr_index_*
+    entries.
 
     torch_scatter=True also makes `import torch_scatter` resolve to dropin_scatter/torch_scatter.py (scatter_mean of
     lgu_slam_amd.aggregate; scatter_sum raises), so droid_slam/droid_net.py imports without torch_scatter.  It raises

@@ -10,7 +10,8 @@ depth frame), built once per call from ii / jj exactly as the reference's schur_
 
 Parity: the kernels are held to the reference's own kernels (tests/test_droid_kernels_vs_reference_build.py, which also
 runs a whole step against them); the assembly and solve, Eigen host code in the reference, to oracle/ba_oracle.py
-(tests/test_ba.py).
+(tests/test_ba.py); the whole call, and that restatement, to the reference's own Python BA (droid_slam/geom/ba.py) at
+lm = 0 within 4x the float32 error of that computation (tests/test_ba_reference.py).
 """
 import os
 

@@ -6,7 +6,8 @@ entries `frame_distance`, `projmap`, `depth_filter`, `iproj` (src/droid.cpp:239-
 DROID's original `corr_index_forward` / `corr_index_backward` (src/droid.cpp:248-249) are outside this build's scope:
 they raise with a pointer to the reference extension instead of silently doing something else.  `ba` raises too unless
 `lgu_slam_amd.install_dropins(experimental_ba=True)` bound it to this build's first device-side bundle adjustment
-(lgu_slam_amd.ba.ba: parity with the reference unpinned).
+(lgu_slam_amd.ba.ba: held to the reference's Python BA at lm = 0 and to a restatement of `ba_cuda` otherwise, see
+DESIGN.md §3.5).
 """
 import lgu_slam_amd.geom as _geom
 import lgu_slam_amd.ops as _ops

@@ -190,6 +190,9 @@ class _Group:
     _QW = 0         # index of qw in the element
     _code = None    # LGU_LIE_* for the groups with kernels
 
+    manifold_dim = 0    # lietorch's names for _T and _K, on the class and on every object
+    embedded_dim = 0    # (droid_slam/geom/ba.py reads poses.manifold_dim)
+
     def __init__(self, data):
         if isinstance(data, _Group):
             data = data.data
@@ -374,6 +377,7 @@ class _Group:
 
 class SO3(_Group):
     _K, _T, _QW, _code = 4, 3, 3, LIE_SO3
+    manifold_dim, embedded_dim = _T, _K
 
     @staticmethod
     def _inv(g):
@@ -411,6 +415,7 @@ class SO3(_Group):
 
 class SE3(_Group):
     _K, _T, _QW, _code = 7, 6, 6, LIE_SE3
+    manifold_dim, embedded_dim = _T, _K
 
     @staticmethod
     def _inv(g):
@@ -458,6 +463,7 @@ class Sim3(_Group):
     """Similarity transforms.  Every operation is the torch composition, on either device: no inference path of the
     reference uses Sim3."""
     _K, _T, _QW, _code = 8, 7, 6, None
+    manifold_dim, embedded_dim = _T, _K
 
     @staticmethod
     def _inv(g):

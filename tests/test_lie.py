@@ -340,6 +340,13 @@ def test_container_semantics(lgu):
     assert G.detach().data.data_ptr() == data.data_ptr()
     assert lie.SE3.Identity(2, 3, dtype=f64, device="cpu").dtype == f64
     assert tuple(lie.SO3.Identity(4).data.shape) == (4, 4) and tuple(lie.Sim3.Identity(4).data.shape) == (4, 8)
+    # lietorch's size attributes (droid_slam/geom/ba.py:36 reads poses.manifold_dim), on classes, objects and views
+    for cls, (tangent, element) in ((lie.SO3, (3, 4)), (lie.SE3, (6, 7)), (lie.Sim3, (7, 8))):
+        obj = cls.Identity(2, 3)
+        assert (cls.manifold_dim, cls.embedded_dim) == (tangent, element)
+        assert (obj.manifold_dim, obj.embedded_dim) == (tangent, element)
+        assert (obj[:, 1:].manifold_dim, obj.inv().embedded_dim) == (tangent, element)
+        assert obj.data.shape[-1] == obj.embedded_dim and obj.log().shape[-1] == obj.manifold_dim
     assert torch.equal(lie.Sim3.Identity(1).data, torch.tensor([[0, 0, 0, 0, 0, 0, 1.0, 1.0]]))
 
 
