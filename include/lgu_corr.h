@@ -1347,6 +1347,50 @@ typedef struct {
 int lgu_intake_frame_u8(lgu_intake_args args, void* stream);
 int lgu_intake_depth_f32(lgu_intake_depth_args args, void* stream);
 
+/* ---- the offscreen view of the map: coloured points and one wireframe frustum per keyframe, z-buffered (csrc/render.hip).
+ * The drawing half of the reference's visualiser: the point actors and camera actors of droid_slam/visualization.py:36-51,
+ * 121-134 in the window of :144-153 with misc/renderoption.json (white background, point size 2).  The definition is
+ * tests/render_restatement.py; DESIGN.md section 3.27 states it in full.  It is this project's own definition of the view:
+ * it was never compared with an Open3D render.
+ *   points (npoints,3) float, world coordinates; colors (npoints,3) RGB, float in [0,1] or with color_u8 the bytes
+ *   view (7) float, world-to-camera t, q(xyzw); intrinsics: fx, fy, cx, cy of the output image; cameras (ncam,7) float,
+ *   world-to-camera, or null with ncam == 0
+ *   image (H,W,3) uint8 RGB; depth (H,W) float: the camera-space z of the winning primitive, +inf on background
+ * Frame buffer: one 64-bit key per pixel in scratch, all ones = empty.  A primitive offers (bits(z) << 32) | (r << 16) |
+ * (g << 8) | b with the float bit pattern of its positive z; a pixel keeps the minimum (64-bit atomic minimum): the nearest
+ * wins, among equal depths the smaller packed colour, whatever the order of points, launches or arrival.
+ * Every float operation rounds on its own.
+ *   point:  Y = act_so3(q, P) + t (the shared definition of csrc/se3.hpp); skipped unless x, y, z are finite and z > near;
+ *           u = fx (x / z) + cx, v = fy (y / z) + cy; x0 = int(floor(u + (1 - 0.5 s))) saturating (NaN: 0), y0 likewise, s =
+ *           point_size; the pixels x0 .. x0 + s - 1 by y0 .. y0 + s - 1 inside the image are offered the key.  A float
+ *           colour becomes the byte clamp(floor(c 255 + 0.5), 0, 255), a NaN 0.
+ *   frustum of camera k: (tr, qr) = rel_se3(cameras[k], view); eight vertices (an apex, a 2 x 2 base at depth 1.5, an
+ *           up-marker on the base's lower edge) times camera_scale, V = act_so3(qr, X) + tr; ten segments A -> B (the base's
+ *           four edges, the four apex edges, the marker's two strokes).  A segment with a non-finite coordinate or both ends
+ *           with !(z >= near) is skipped; one end with !(z >= near) is replaced by A + tc (B - A), tc = (near - A.z) / (B.z -
+ *           A.z), with z = near exactly.  Ends are projected as points are, w = 1 / z; n = ceil(max(|ub - ua|, |vb - va|)),
+ *           1 if 0; a non-finite n or n > 2^20 skips the segment.  Sample k = 0 .. n: tk = float(k) / n, u = ua + tk (ub -
+ *           ua), v and w likewise, z = 1 / w; it offers (bits(z), camera_color) to pixel (floor(u + 0.5), floor(v + 0.5)) if
+ *           inside the image.
+ *   resolve: an empty pixel gets background and +inf, any other the key's three bytes and the float of its high word.
+ * Launches: clear, points (npoints > 0), lines (ncam > 0, one wave per camera), resolve; all on `stream`, no host
+ * synchronisation.  scratch: lgu_render_scratch_bytes(H, W) = 8 H W bytes of device memory (0 for an empty or negative
+ * size), 16-byte aligned (else LGU_E_BADARG); it needs no initialisation.  Other operands at element alignment.
+ * Negative sizes, point_size outside 1..8, a near that is not finite and positive, a non-finite camera_scale, a null operand
+ * that the sizes need: LGU_E_BADARG.  H W > 2^28: LGU_E_UNSUPPORTED.  H W == 0: nothing is launched.  Every refusal comes
+ * before any launch.  The operands travel in one parameter block passed by value. */
+typedef struct {
+  const float* points; const void* colors; const float* view; const float* intrinsics;
+  const float* cameras;                                                /* or null */
+  void* scratch; unsigned char* image; float* depth;
+  long long npoints;
+  float near, camera_scale;
+  int ncam, H, W, point_size, color_u8;
+  unsigned char background[3]; unsigned char camera_color[3];
+} lgu_render_args;
+long long lgu_render_scratch_bytes(int H, int W);
+int lgu_render_view(lgu_render_args args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ module `lgu_slam_amd.py` at the repository root.
 import os
 import sys
 
-from . import _build, _lib, aggregate, ba, cloud, context, conv1, conv3, encconv, encoder, features, flow, geom, graph, gru, heads, intake, lie, ops, sharded, upmask  # noqa: F401
+from . import _build, _lib, aggregate, ba, cloud, context, conv1, conv3, encconv, encoder, features, flow, geom, graph, gru, heads, intake, lie, ops, render, sharded, upmask  # noqa: F401
 from . import update  # noqa: F401
 from .conv1 import Conv1  # noqa: F401
 from .conv3 import Conv3, Conv3Stack, conv3x3_fanout  # noqa: F401

@@ -111,6 +111,14 @@ class CloudArgs(ctypes.Structure):
                 ("stride", _int), ("phase", _int), ("color_u8", _int)]
 
 
+class RenderArgs(ctypes.Structure):
+    """lgu_render_args of include/lgu_corr.h, passed by value."""
+    _fields_ = [("points", _vp), ("colors", _vp), ("view", _vp), ("intrinsics", _vp), ("cameras", _vp), ("scratch", _vp),
+                ("image", _vp), ("depth", _vp), ("npoints", ctypes.c_longlong), ("near", ctypes.c_float),
+                ("camera_scale", ctypes.c_float), ("ncam", _int), ("H", _int), ("W", _int), ("point_size", _int), ("color_u8", _int),
+                ("background", ctypes.c_ubyte * 3), ("camera_color", ctypes.c_ubyte * 3)]
+
+
 class IntakeCamera(ctypes.Structure):
     """lgu_intake_camera of include/lgu_corr.h: 22 doubles."""
     _fields_ = [("k", ctypes.c_double * 4), ("kn", ctypes.c_double * 4), ("ir", ctypes.c_double * 9), ("d", ctypes.c_double * 5)]
@@ -283,10 +291,14 @@ SIGNATURES = {
     # path} by value, stream; {raw, out, scale, N, h0, w0, h1, w1, top, left, H, W, src_u16} by value, stream
     "lgu_intake_frame_u8": [IntakeArgs, _vp],
     "lgu_intake_depth_f32": [IntakeDepthArgs, _vp],
+    # the offscreen view: {points, colors, view, intrinsics, cameras, scratch, image, depth, npoints, near, camera_scale, ncam,
+    # H, W, point_size, color_u8, background[3], camera_color[3]} by value, stream
+    "lgu_render_view": [RenderArgs, _vp],
     # size queries (host only) and the library's own description
     "lgu_ba_solve_blocked_work_doubles": [_int],
     "lgu_offsets_finalize_scratch_bytes": [_int],
     "lgu_cloud_scratch_bytes": [_int] * 3,
+    "lgu_render_scratch_bytes": [_int] * 2,
     "lgu_proximity_prefix_len": [_int] * 4,
     "lgu_proximity_capacity": [_int] * 5 + [ctypes.c_longlong],
     "lgu_proximity_work_bytes": [_int] * 3,
@@ -296,7 +308,7 @@ SIGNATURES = {
 }
 RESTYPES = {name: ctypes.c_longlong for name in (
     "lgu_ba_solve_blocked_work_doubles", "lgu_offsets_finalize_scratch_bytes", "lgu_proximity_prefix_len", "lgu_proximity_capacity",
-    "lgu_proximity_work_bytes", "lgu_cloud_scratch_bytes")}
+    "lgu_proximity_work_bytes", "lgu_cloud_scratch_bytes", "lgu_render_scratch_bytes")}
 RESTYPES.update(lgu_instnorm_resident_limit=ctypes.c_long, lgu_version=ctypes.c_char_p, lgu_error_string=ctypes.c_char_p)
 
 _lib = None
