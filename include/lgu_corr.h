@@ -641,7 +641,7 @@ int lgu_kangru_blend_h16(const void* cq, const void* kq, const void* z, const vo
  *   LGU_E_UNSUPPORTED): marking, 63-bit keys, a bitonic sort of the keys in LDS, the prefix and the greedy pass.
  * lgu_proximity_keys           marking and key build for any n: work (lgu_proximity_work_bytes(), 4-byte aligned) becomes
  *   the bitmap of the known edges' diamonds (bit f), keys[f] (n int64) = (m(d) << 31) | f >= 0 with m the order-preserving
- *   32-bit image of d's bits, or INT64_MAX for a dead cell or d > thresh.  A memset and two launches.
+ *   32-bit image of d's bits, or INT64_MAX for a dead cell or d > thresh.  Three launches (the first clears work).
  * lgu_proximity_select_sorted  the prefix and the greedy pass over keys SORTED ascending as signed 64-bit integers (by any
  *   sort), one workgroup; work as lgu_proximity_keys left it (it is modified).  The greedy pass takes 64 keys at a time, one per
  *   lane: the lowest live lane is accepted, every lane drops its own candidate if it lies in the accepted diamond, the diamond

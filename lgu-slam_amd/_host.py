@@ -173,9 +173,30 @@ def param_key(tensors):
     return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
 
 
+def capturing(device=None):
+    """The current stream of `device` (default: the current device) is recording a graph.  What is made then is only
+    recorded, not run, and lives in the graph's private memory pool: every cache of the package uses such a value for the
+    call and does not keep it; a value kept from before the capture is used as it is."""
+    if not torch.cuda.is_available():
+        return False
+    if device is None or device.index is None or device.index == torch.cuda.current_device():
+        return torch.cuda.is_current_stream_capturing()
+    with torch.cuda.device(device):
+        return torch.cuda.is_current_stream_capturing()
+
+
+def no_upload_while_capturing(what, device=None):
+    """Refusal of a host table that would have to be uploaded while the stream records a graph: the copy waits for the
+    host, which a capture does not allow, and its contents are indices.  Callers ask before the launches the table serves."""
+    if capturing(device):
+        raise RuntimeError("%s: its index table has to be uploaded, which a stream that is capturing a graph cannot do; "
+                           "make the same call once before the capture" % what)
+
+
 class PackCache:
     """Packed weights, one entry per slot, each kept while the parameters it was made of are what they were (`param_key`):
-    load_state_dict, in-place updates and moves make a new pack, which replaces the slot's old one."""
+    load_state_dict, in-place updates and moves make a new pack, which replaces the slot's old one.  A pack made while the
+    stream is capturing a graph serves that call and is not kept (`capturing`)."""
 
     def __init__(self):
         self._slots = {}
@@ -185,6 +206,8 @@ class PackCache:
         key = (extra, param_key(tensors))
         hit = self._slots.get(slot)
         if hit is None or hit[0] != key:
+            if capturing(tensors[0].device if len(tensors) and tensors[0].is_cuda else None):   # asked on a miss only
+                return make()
             hit = (key, make())
             self._slots[slot] = hit
         return hit[1]

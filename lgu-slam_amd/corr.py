@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, ops
+from ._host import capturing, no_upload_while_capturing
 
 
 class CorrSampler(torch.autograd.Function):
@@ -92,6 +93,13 @@ class _Snapshot:
                 and self.marks == tuple((t._version, t.data_ptr()) for t in tensors))
 
 
+def _kept(tensors):
+    """The snapshot under which a derivative of `tensors` is kept — None while the stream is capturing a graph: what was
+    made then was only recorded and lives in the graph's pool, so it serves the call that made it and the next call
+    derives it again (every reader treats a None snapshot as a miss)."""
+    return None if capturing(tensors[0].device if tensors[0].is_cuda else None) else _Snapshot(tensors)
+
+
 def _zero_offsets(like, n):
     """A structurally-zero offset level (reference corr.py:132-135) for n edges without n copies of it: one zero row
     expanded over the edge dimension (stride 0).  The samplers never read or write these levels (they get NULL), and
@@ -101,7 +109,9 @@ def _zero_offsets(like, n):
     if row is None:   # one zero row per shape / dtype / device for the life of the process (a fill launch per call otherwise);
         if len(_ZERO_ROWS) >= 16:   # nothing writes through a stride-0 expansion, so sharing the row is safe
             _ZERO_ROWS.clear()
-        row = _ZERO_ROWS[key] = torch.zeros((1,) + key[0], dtype=like.dtype, device=like.device)
+        row = torch.zeros((1,) + key[0], dtype=like.dtype, device=like.device)
+        if not capturing(like.device if like.is_cuda else None):   # a fill that was only recorded is not kept
+            _ZERO_ROWS[key] = row
     return row.expand((n,) + key[0])
 
 
@@ -146,7 +156,8 @@ def _half_pack(conv):
     if kept is None or not kept[0].matches(params):
         kept = (_Snapshot(params), ops.pack_offset_conv(conv.weight.detach().half().float(), conv.bias.detach().half().float(),
                                                         scale=1.0))
-        conv._lgu_half_pack = kept
+        if not capturing(conv.weight.device if conv.weight.is_cuda else None):   # made while recording: this call only
+            conv._lgu_half_pack = kept
     return kept[1]
 
 
@@ -345,6 +356,7 @@ class CorrBlock:
 
     def _slots(self):
         if self._slots_dev is None or self._slots_dev.shape[0] != len(self._slot_list):
+            no_upload_while_capturing("CorrBlock", self._store[0].device)
             self._slots_dev = torch.tensor(self._slot_list, dtype=torch.int32, device=self._store[0].device)
         return self._slots_dev
 
@@ -403,6 +415,7 @@ class CorrBlock:
                    .view(batch, num, -1, ht, wd) for i in range(self.num_levels)]
             return torch.cat(out, dim=2), self.mean_n, self.theta
 
+        slots = self._slots() if self._store is not None else None   # (first: refuses, before any launch, what a capture cannot upload)
         offs = []
         for i in range(self.num_levels):
             if self._zero_level[i]:
@@ -410,13 +423,16 @@ class CorrBlock:
                 continue
             o = self.offset[i]
             if o.dtype != torch.float32 or not o.is_contiguous():
+                if o.is_cuda and capturing(o.device):   # the converted buffer is state the block keeps: not from a graph's pool
+                    raise RuntimeError("CorrBlock: its offsets have to be converted to contiguous float32 first, and a buffer "
+                                       "made while a graph is captured cannot be kept; make the same call once before the capture")
                 o = o.float().contiguous()
                 self.offset[i] = o  # keep the buffer the kernel zeroes the centre of
             offs.append(o.view(E, ht, wd, rd, rd, 2))
         if self._store is not None:
-            pyr, slots = self._store, self._slots()
+            pyr = self._store
         else:
-            pyr, slots = [v if v.is_contiguous() else v.contiguous() for v in self._pyr], None
+            pyr = [v if v.is_contiguous() else v.contiguous() for v in self._pyr]
         # inference: probe + mask + all levels + concatenation in ONE launch; offset[1] is
         # scaled in place by the kernel (the same persistent state as above).  The prepared
         # launch is rebuilt only when the pyramid / offset buffers change (cat, __getitem__).
@@ -558,9 +574,9 @@ class AltCorrBlock:
         if self.pyramid[0].dtype != torch.float16:
             frames = [f.float() for f in frames]
         if (getattr(self, "_chunked", None) is None or self._chunked[0].dtype != frames[0].dtype
-                or not self._chunked_snap.matches(self.pyramid)):    # rewritten / replaced levels: re-derive
+                or self._chunked_snap is None or not self._chunked_snap.matches(self.pyramid)):    # rewritten / replaced levels: re-derive
             self._chunked = [ops.lowmem_chunked(f) for f in frames]
-            self._chunked_snap = _Snapshot(self.pyramid)
+            self._chunked_snap = _kept(self.pyramid)
         return frames
 
     def call_many(self, coords, ii, jj, counts):
@@ -590,10 +606,12 @@ class AltCorrBlock:
                 and self.num_levels >= 2 and self.pyramid[0].dtype == torch.float16 and ii.dtype == torch.int64
                 and jj.dtype == torch.int64):
             return one_by_one()
+        K = len(counts)
+        ckey = (tuple(counts), ii.device)
+        if getattr(self, "_calls_key", None) != ckey:   # refused before anything is launched
+            no_upload_while_capturing("AltCorrBlock.call_many", ii.device)
         try:
             frames = self._frame_operands()
-            K = len(counts)
-            ckey = (tuple(counts), ii.device)
             if getattr(self, "_calls_key", None) != ckey:   # edge -> call tables, uploaded once per partition
                 self._calls_first = torch.tensor(starts, device=ii.device)
                 self._calls_row = torch.repeat_interleave(torch.arange(K, dtype=torch.int32, device=ii.device),
@@ -652,13 +670,13 @@ class AltCorrBlock:
         if getattr(self, "_ofs_snap", None) is None or not self._ofs_snap.matches(heads):
             self._ofs_packed = ops.pack_offset_conv(conv.weight, conv.bias)
             self._res_packed = ops.pack_offset_conv(res.weight, res.bias) if res_fast else None
-            self._ofs_snap = _Snapshot(heads)
+            self._ofs_snap = _kept(heads)
             self._head_snap = None       # the per-frame partial convolutions were made with the old weights
         level0 = self.pyramid[0]
         frames0 = level0[0]
-        if (getattr(self, "_pooled", None) is None or not self._pooled_snap.matches([level0])
+        if (getattr(self, "_pooled", None) is None or self._pooled_snap is None or not self._pooled_snap.matches([level0])
                 or self._pooled_fast != res_fast):
-            self._pooled_snap, self._pooled_fast = _Snapshot([level0]), res_fast
+            self._pooled_snap, self._pooled_fast = _kept([level0]), res_fast
             self._head_snap = None       # ... or from the old frames
             # 2 x 2 averages of the frames in fp32, as avg_pool2d of the reference's fp32 input gives them (x 4 is a power
             # of two and moves to the weights exactly), channel-last, split into two half parts: hi + lo == the average
@@ -682,7 +700,7 @@ class AltCorrBlock:
                     self._head0 = ops.OffsetHeadCache(frames0, ops.pack_offset_conv_parts(conv.weight, conv.bias))
                     self._head1 = ops.OffsetHeadCache(self._pooled[0], ops.pack_offset_conv_parts(res.weight, res.bias),
                                                       frames_lo=self._pooled[1])
-                    self._head_snap = True
+                    self._head_snap = None if capturing(frames0.device) else True
                 E = iic.shape[0]
                 work = self._head0.mark(iic, jjc)   # one claim pass for both heads: they need the same frames
                 self._head0.convolve(work, E)

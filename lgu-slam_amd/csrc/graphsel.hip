@@ -219,6 +219,13 @@ __global__ __launch_bounds__(GS_THREADS) void proximity_mark_kernel(const long l
   if (e < nk) gs_mark_known(bm, kii, kjj, e, w);
 }
 
+// The bitmap is cleared by a kernel, not by hipMemsetAsync: recorded into a graph that call becomes a memset node, and a
+// second replay of such a graph left other bytes than zero in `work` (tests/test_capture.py).
+__global__ __launch_bounds__(GS_THREADS) void proximity_clear_kernel(unsigned* __restrict__ bm, int words) {
+  const int k = blockIdx.x * GS_THREADS + threadIdx.x;
+  if (k < words) bm[k] = 0u;
+}
+
 __global__ __launch_bounds__(GS_THREADS) void proximity_keys_kernel(const float* __restrict__ dist, const unsigned* __restrict__ bm,
                                                                     GsWin w, long long* __restrict__ keys) {
   const int f = blockIdx.x * GS_THREADS + threadIdx.x;
@@ -306,7 +313,10 @@ int lgu_proximity_select_small(const float* dist, const long long* known_ii, con
   if (n > GS_SMALL_MAX) return LGU_E_UNSUPPORTED;
   if (num_known < 0 || max_factors > LLONG_MAX - 2 || !count) return LGU_E_BADARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);   // no rows: the prefix is empty
+  if (n == 0) {   // no rows: the prefix is empty
+    hipLaunchKernelGGL(proximity_clear_kernel, dim3(1), dim3(GS_THREADS), 0, st, reinterpret_cast<unsigned*>(count), 1);
+    return launch_status();
+  }
   const long long prefix = gs_prefix(t, t0, rad, stereo);
   if (prefix > GS_MAX_PREFIX || capacity < gs_capacity(prefix, max_factors, n)) return LGU_E_BADARG;
   if (!dist || !e_ii || !e_jj || (num_known > 0 && (!known_ii || !known_jj))) return LGU_E_BADARG;
@@ -330,8 +340,11 @@ int lgu_proximity_keys(const float* dist, const long long* known_ii, const long 
   if ((reinterpret_cast<uintptr_t>(work) & 3) != 0) return LGU_E_BADARG;  // the bitmap is read and or-ed as 32-bit words
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const GsWin w = gs_window(t, t0, t1, rad, nms, thresh, stereo, n);
-  const hipError_t e = hipMemsetAsync(work, 0, (size_t)(4 * ((n + 31) / 32)), st);
-  if (e != hipSuccess) return (int)e;
+  const int words = (int)((n + 31) / 32);   // n <= GS_MAX_CELLS = 2^24
+  hipLaunchKernelGGL(proximity_clear_kernel, dim3((unsigned)((words + GS_THREADS - 1) / GS_THREADS)), dim3(GS_THREADS), 0, st,
+                     reinterpret_cast<unsigned*>(work), words);
+  const int rz = launch_status();
+  if (rz != LGU_OK) return rz;
   if (num_known > 0) {
     hipLaunchKernelGGL(proximity_mark_kernel, dim3((num_known + GS_THREADS - 1) / GS_THREADS), dim3(GS_THREADS), 0, st, known_ii,
                        known_jj, num_known, w, reinterpret_cast<unsigned*>(work));
@@ -352,7 +365,10 @@ int lgu_proximity_select_sorted(const long long* sorted_keys, void* work, int t,
   if (rc != LGU_OK) return rc;
   if (max_factors > LLONG_MAX - 2 || !count) return LGU_E_BADARG;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n == 0) return (int)hipMemsetAsync(count, 0, sizeof(int), st);
+  if (n == 0) {
+    hipLaunchKernelGGL(proximity_clear_kernel, dim3(1), dim3(GS_THREADS), 0, st, reinterpret_cast<unsigned*>(count), 1);
+    return launch_status();
+  }
   const long long prefix = gs_prefix(t, t0, rad, stereo);
   if (prefix > GS_MAX_PREFIX || capacity < gs_capacity(prefix, max_factors, n)) return LGU_E_BADARG;
   if (!sorted_keys || !work || !e_ii || !e_jj) return LGU_E_BADARG;

@@ -11,6 +11,8 @@ ReLU kernels, and the 3x3 convolution then receives the channel-last half tensor
 import torch
 import torch.nn.functional as F
 
+from ._host import capturing
+
 
 class CorrEncoder:
     """Drop-in for calling the reference's `corr_encoder` Sequential.
@@ -41,10 +43,13 @@ class CorrEncoder:
                c2.bias._version)
         if key != self._key:
             with torch.no_grad():
-                self._w1t = c1.weight.view(c1.out_channels, c1.in_channels).half().contiguous().t()  # (196,128) view
-                self._b1 = c1.bias.half().contiguous()
-                self._w2 = c2.weight.half().contiguous(memory_format=torch.channels_last)
-                self._b2 = c2.bias.half().contiguous()
+                made = (c1.weight.view(c1.out_channels, c1.in_channels).half().contiguous().t(),  # (196,128) view
+                        c1.bias.half().contiguous(),
+                        c2.weight.half().contiguous(memory_format=torch.channels_last),
+                        c2.bias.half().contiguous())
+            if capturing(c1.weight.device if c1.weight.is_cuda else None):   # only recorded, in the graph's pool: this call only
+                return made
+            self._w1t, self._b1, self._w2, self._b2 = made
             self._key = key
         return self._w1t, self._b1, self._w2, self._b2
 
@@ -57,7 +62,10 @@ class CorrEncoder:
         key = (c1.weight.data_ptr(), c1.weight._version, c1.bias._version)
         if getattr(self, "_fkey", None) != key:
             from . import ops
-            self._fused = ops.pack_encoder_layer(c1.weight, c1.bias)
+            made = ops.pack_encoder_layer(c1.weight, c1.bias)
+            if capturing(c1.weight.device):   # made while a graph is recorded: serves this call, is not kept
+                return made
+            self._fused = made
             self._fkey = key
         return self._fused
 

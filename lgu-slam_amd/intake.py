@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, features
-from ._host import check_contiguous, check_device, check_dtype, check_no_grad, check_shape, launch
+from ._host import check_contiguous, check_device, check_dtype, check_no_grad, check_shape, launch, no_upload_while_capturing
 from ._host import ptr as _ptr, stream as _stream
 
 MIN_FUSED_PIXELS = 0        # N*H*W below which frame takes frame_composed (read at the call)
@@ -96,6 +96,7 @@ class Plan:
         """The cameras as a device table (ncam,22) float64, uploaded once per device."""
         t = self._tables.get(device)
         if t is None:
+            no_upload_while_capturing("intake.Plan.table", device if isinstance(device, torch.device) else torch.device(device))
             t = self._tables[device] = torch.from_numpy(self.cameras).to(device)
         return t
 

@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._host import CurrentDevice, check_contiguous, check_operands, dtype_name, launch
+from ._host import CurrentDevice, capturing, check_contiguous, check_operands, dtype_name, launch
 from ._host import _vp, ptr as _ptr, stream as _stream  # noqa: F401  (tests and tools read ops._vp, ops._ptr, ops._stream)
 
 
@@ -629,12 +629,15 @@ class OffsetHeadCache:
         E = ii.shape[0]
         if 2 * E > 65535:   # the worklist convolution sizes its grid with 2E
             raise _lib.UnsupportedShape("OffsetHeadCache: at most 32767 edges per call")
-        if self.worklist is None or self.worklist.numel() < 2 * E:
-            self.worklist = torch.empty(max(2 * E, 64), dtype=torch.int32, device=self.frames.device)
+        worklist = self.worklist
+        if worklist is None or worklist.numel() < 2 * E:
+            worklist = torch.empty(max(2 * E, 64), dtype=torch.int32, device=self.frames.device)
+            if not capturing(self.frames.device):   # a list made while a graph is recorded serves that call only
+                self.worklist = worklist
         if E:
             launch("lgu_offset_heads_mark", "offset_heads_mark", self.frames.device, _ptr(ii), _ptr(jj), E, _ptr(self.done), self.NF,
-                   _ptr(self.worklist), _ptr(self.count), _stream(self.frames))
-        return self.worklist, self.count
+                   _ptr(worklist), _ptr(self.count), _stream(self.frames))
+        return worklist, self.count
 
     def convolve(self, work, E):
         """Partial convolutions of the frames on the worklist `work` = (worklist, count) of a mark pass over E edges."""

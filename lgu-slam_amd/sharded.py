@@ -21,6 +21,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from ._host import no_upload_while_capturing
+
 
 def balanced_shard(n_edges, rank, world):
     """Contiguous, balanced [lo, hi) range of edge indices for `rank` (frontend path)."""
@@ -110,6 +112,8 @@ class RowExchange:
     def _index(self, dev):
         """The three index tensors on the data's device (uploaded once per device, not per call)."""
         if dev not in self._dev:
+            if dev.type == "cuda" and any(t is not None and t.device != dev for t in (self.all_ids, self.src, self.src_by_id)):
+                no_upload_while_capturing("sharded index tables", dev)      # refused before anything is launched
             self._dev[dev] = tuple(t.to(dev) if t is not None else None for t in (self.all_ids, self.src, self.src_by_id))
         return self._dev[dev]
 

@@ -1113,6 +1113,333 @@ case("ba.ba", ["lgu_ba_build_f32", "lgu_ba_accum_f32", "lgu_ba_depth_system_f32"
 
 
 # ======================================================================================================================
+# The entries that take a parameter block by value (DESIGN.md sections 3.14-3.27), through their operator functions at
+# (2, 9, 33): an odd width, two images, more than one tile.  Their operands at element alignment are served with the
+# aligned call's bits; a pack (wpack, dpack) below 16 bytes is LGU_E_UNSUPPORTED.  The outputs these functions allocate
+# themselves are shifted by the per-file tests (test_guard_bands_and_alignment of each operator's own file).
+# ======================================================================================================================
+PACK = A16("unsupported")
+_N, _H, _W = 2, 9, 33
+
+
+def _conv_w(g, cout, cin, k, dev, bias_scale=0.1):
+    return _randn(g, (cout, cin, k, k), dev, (cin * k * k) ** -0.5), _randn(g, (cout,), dev, bias_scale)
+
+
+def _layer_inputs(seed, cin, pack, x_half, extra=None):
+    """x (2,cin,9,33) float32 or half, (wpack, bias) of pack(lgu)(weight, bias)."""
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(seed)
+        a = dict(x=_randn(g, (_N, cin, _H, _W), dev, 1.0, torch.float16 if x_half else torch.float32))
+        a["wpack"], a["bias"] = pack(lgu, g, dev)
+        if extra:
+            extra(lgu, g, dev, a)
+        return a
+    return build
+
+
+_XWB = dict(x=SAME, wpack=PACK, bias=SAME)
+
+case("flow.flow_conv7_relu", ["lgu_flow_conv7_relu_h16"], "own",
+     _layer_inputs(201, 4, lambda lgu, g, dev: lgu.flow.pack_conv7(*_conv_w(g, 128, 4, 7, dev)), False),
+     lambda lgu, a: (lgu.flow.flow_conv7_relu(a["x"], a["wpack"], a["bias"]),), _XWB)
+for _h, _co in ((False, 64), (True, 128)):
+    case("conv3.conv3x3[%s x, Cout %d]" % ("h16" if _h else "f32", _co), ["lgu_conv3x3_c128_h16"], "own",
+         _layer_inputs(203 + _co, 128, (lambda co: lambda lgu, g, dev: lgu.conv3.pack_conv3(*_conv_w(g, co, 128, 3, dev)))(_co), _h),
+         lambda lgu, a: (lgu.conv3.conv3x3(a["x"], a["wpack"], a["bias"], relu=True),), _XWB)
+
+
+def _fanout_inputs(x_half):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(207)
+        a = dict(x=_randn(g, (_N, 128, _H, _W), dev, 1.0, torch.float16 if x_half else torch.float32))
+        for i in range(3):
+            a["w%d" % i], a["b%d" % i] = lgu.conv3.pack_conv3(*_conv_w(g, 128, 128, 3, dev))
+        return a
+    return build
+
+
+for _h in (False, True):
+    case("conv3.conv3x3_fanout[%s x]" % ("h16" if _h else "f32"), ["lgu_conv3x3_fanout_c128_h16"], "own", _fanout_inputs(_h),
+         lambda lgu, a: tuple(lgu.conv3.conv3x3_fanout(a["x"], [(a["w%d" % i], a["b%d" % i]) for i in range(3)], relu=True)),
+         dict(x=SAME, w0=PACK, w1=PACK, w2=PACK, b0=SAME, b1=SAME, b2=SAME))
+for _h, _co, _act in ((False, 2, "none"), (True, 2, "sigmoid"), (False, 1, "softplus")):
+    case("heads.head_conv3x3[%s x, Cout %d, %s]" % ("h16" if _h else "f32", _co, _act), ["lgu_head3x3_c128_h16"], "own",
+         _layer_inputs(211 + _co, 128, (lambda co: lambda lgu, g, dev: lgu.heads.pack_head(*_conv_w(g, co, 128, 3, dev)))(_co), _h),
+         (lambda act: lambda lgu, a: (lgu.heads.head_conv3x3(a["x"], a["wpack"], a["bias"], act=act),))(_act), _XWB)
+
+
+def _pair_inputs(x_half, f32):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(217)
+        dt = torch.float16 if x_half else torch.float32
+        a = dict(d=_randn(g, (_N, 128, _H, _W), dev, 1.0, dt), w=_randn(g, (_N, 128, _H, _W), dev, 1.0, dt))
+        a["wd"], a["bd"] = lgu.heads.pack_head(*_conv_w(g, 2, 128, 3, dev))
+        a["ww"], a["bw"] = lgu.heads.pack_head(*_conv_w(g, 2, 128, 3, dev))
+        if f32:
+            a["coords"] = _randn(g, (1, _N, _H, _W, 2), dev, 8.0)
+        return a
+    return build
+
+
+for _h, _f in ((False, False), (True, True)):
+    _ops = dict(d=SAME, w=SAME, wd=PACK, ww=PACK, bd=SAME, bw=SAME)
+    if _f:
+        _ops["coords"] = A8("unsupported")      # a whole (x, y) pair per access
+    case("heads.head_pair[%s x%s]" % ("h16" if _h else "f32", ", coords" if _f else ""), ["lgu_head3x3_pair_c128_h16"], "own",
+         _pair_inputs(_h, _f),
+         lambda lgu, a: tuple(lgu.heads.head_pair(a["d"], a["w"], (a["wd"], a["bd"]), (a["ww"], a["bw"]), coords=a.get("coords"))), _ops)
+
+
+def _gruconv_inputs(mode):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(223)
+        h16 = torch.float16
+        convs = []
+        for _ in range(2 if mode == "zr" else 1):
+            c = torch.nn.Conv2d(448, 128, 3, padding=1)
+            with torch.no_grad():
+                w, b = _conv_w(g, 128, 448, 3, "cpu")
+                c.weight.copy_(w)
+                c.bias.copy_(b)
+            convs.append(c.to(dev))
+        a = {"seg%d" % i: _randn(g, (_N, ch, _H, _W), dev, 1.0, h16) for i, ch in enumerate((128, 128, 128, 64))}
+        a["wpack"], a["bias"] = lgu.gru.pack_gruconv(convs if mode == "zr" else convs[0])
+        if mode != "plain":
+            a["k0"], a["net"] = _randn(g, (_N, 128), dev, 1.0, h16), _randn(g, (_N, 128, _H, _W), dev, 1.0, h16)
+        if mode == "zr":
+            a["k1"] = _randn(g, (_N, 128), dev, 1.0, h16)
+        if mode == "q":
+            a["z"] = torch.rand((_N, 128, _H, _W), generator=g).to(h16).to(dev)
+        return a
+    return build
+
+
+def _gruconv_call(mode):
+    def call(lgu, a):
+        segs = [a["seg%d" % i] for i in range(4)]
+        if mode == "plain":
+            return (lgu.gru.gru_conv3x3(segs, a["wpack"], a["bias"]),)
+        if mode == "zr":
+            return tuple(lgu.gru.gru_conv_zr(segs, a["wpack"], a["bias"], a["k0"], a["k1"], a["net"]))
+        return (lgu.gru.gru_conv_q(segs, a["wpack"], a["bias"], a["k0"], a["z"], a["net"]),)
+    return call
+
+
+for _m, _more in (("plain", ()), ("zr", ("k0", "k1", "net")), ("q", ("k0", "z", "net"))):
+    _ops = dict({"seg%d" % i: SAME for i in range(4)}, wpack=PACK, bias=SAME)
+    _ops.update({k: SAME for k in _more})
+    case("gru.gru_conv[%s]" % _m, ["lgu_gruconv3x3_c448_h16"], "own", _gruconv_inputs(_m), _gruconv_call(_m), _ops)
+
+for _h in (False, True):
+    case("upmask.upmask_conv1x1[%s x]" % ("h16" if _h else "f32"), ["lgu_upmask1x1_c128_h16"], "own",
+         _layer_inputs(227, 128, lambda lgu, g, dev: lgu.upmask.pack_upmask(*_conv_w(g, 576, 128, 1, dev)), _h),
+         lambda lgu, a: (lgu.upmask.upmask_conv1x1(a["x"], a["wpack"], a["bias"]),), _XWB)
+
+
+def _ups_net_inputs(x_half):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(229)
+        U, N, ht, wd = 2, 4, 5, 7
+        a = dict(x=_randn(g, (U, 128, ht, wd), dev, 1.0, torch.float16 if x_half else torch.float32))
+        a["wpack"], a["bias"] = lgu.upmask.pack_upmask(*_conv_w(g, 576, 128, 1, dev))
+        a.update(disps=_randn(g, (N, ht, wd), dev).abs() + 0.1, ix=torch.tensor([3, 1], dtype=torch.int64).to(dev),
+                 disps_up=torch.full((N, 8 * ht, 8 * wd), -3.0, device=dev))
+        return a
+    return build
+
+
+for _h in (False, True):
+    # disps_up is written as 16-byte quads, like aggregate.upsample_disps_
+    case("upmask.upsample_from_net_[%s x]" % ("h16" if _h else "f32"), ["lgu_upmask_upsample_f32"], "own", _ups_net_inputs(_h),
+         lambda lgu, a: (lgu.upmask.upsample_from_net_(a["disps_up"], a["disps"], a["ix"], a["x"], a["wpack"], a["bias"],
+                                                       half_weights=True).clone(),),
+         dict(x=SAME, wpack=PACK, bias=SAME, disps=SAME, ix=SAME, disps_up=A16("unsupported")), inplace=("disps_up",))
+
+for _h, _ci in ((False, 196), (True, 98)):
+    case("conv1.conv1x1[%s x, Cin %d]" % ("h16" if _h else "f32", _ci), ["lgu_conv1x1_o128_h16"], "own",
+         _layer_inputs(233 + _ci, _ci, (lambda ci: lambda lgu, g, dev: lgu.conv1.pack_conv1(*_conv_w(g, 128, ci, 1, dev)))(_ci), _h),
+         (lambda ci: lambda lgu, a: (lgu.conv1.conv1x1(a["x"], a["wpack"], a["bias"], cin=ci, relu=True),))(_ci), _XWB)
+
+
+# ---- the encoders' convolutions: (32, 64, stride 2) with the downsample branch, (64, 64, 1) with a residual -----------
+def _enc_inputs(cin, cout, stride, residual=False):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(239 + cout + stride)
+        a = dict(x=_randn(g, (_N, cin, _H, _W), dev, 1.0, torch.float16))
+        a["wpack"], a["bias"] = lgu.encconv.pack_enc3(*_conv_w(g, cout, cin, 3, dev))
+        if stride == 2:
+            a["dpack"], a["dbias"] = lgu.encconv.pack_enc1(*_conv_w(g, cout, cin, 1, dev))
+        if residual:
+            a["res"] = _randn(g, (_N, cout) + tuple(lgu.encconv.out_size(_H, _W, stride)), dev, 1.0, torch.float16)
+        return a
+    return build
+
+
+def _enc_call(lgu, a):
+    stride = 2 if "dpack" in a else 1
+    got = lgu.encconv.enc_conv3x3(a["x"], (a["wpack"], a["bias"]), stride=stride, relu="res" not in a, residual=a.get("res"),
+                                  down=(a["dpack"], a["dbias"]) if stride == 2 else None)
+    return tuple(got) if stride == 2 else (got,)
+
+
+case("encconv.enc_conv3x3[32-64-s2, down]", ["lgu_encconv3x3_h16"], "own", _enc_inputs(32, 64, 2), _enc_call,
+     dict(x=SAME, wpack=PACK, bias=SAME, dpack=PACK, dbias=SAME))
+case("encconv.enc_conv3x3[64-64-s1, residual]", ["lgu_encconv3x3_h16"], "own", _enc_inputs(64, 64, 1, residual=True), _enc_call,
+     dict(x=SAME, wpack=PACK, bias=SAME, res=SAME))
+
+for _h in (False, True):
+    case("encconv.enc_stem7x7[%s x]" % ("h16" if _h else "f32"), ["lgu_encstem7x7_h16"], "own",
+         _layer_inputs(241, 3, lambda lgu, g, dev: lgu.encconv.pack_stem(*_conv_w(g, 32, 3, 7, dev)), _h),
+         lambda lgu, a: (lgu.encconv.enc_stem7x7(a["x"], (a["wpack"], a["bias"]), relu=True),), _XWB)
+for _co, _split in ((128, False), (256, True)):
+    case("encconv.enc_out1x1[Cout %d%s]" % (_co, ", split" if _split else ""), ["lgu_encout1x1_c128_h16"], "own",
+         _layer_inputs(243 + _co, 128, (lambda co: lambda lgu, g, dev: lgu.encconv.pack_out1(*_conv_w(g, co, 128, 1, dev)))(_co), True),
+         (lambda sp: lambda lgu, a: (lambda r: tuple(r) if sp else (r,))(lgu.encconv.enc_out1x1(a["x"], (a["wpack"], a["bias"]), split=sp)))(
+             _split), _XWB)
+
+
+def _encnorm_inputs(dev):
+    """x and y with the exact sums of their planes (made by two emitting launches), and the (32, 64, 2) layer with its
+    branch that reads them: RES_NORM with keep and emit, every pointer of the block in use."""
+    import lgu_slam_amd as lgu
+    E = lgu.encconv
+    g = _gen(251)
+    x0 = _randn(g, (_N, 32, _H, _W), dev, 1.0, torch.float16)
+    a = {}
+    for k, s in (("x", "stats_x"), ("y", "stats_y")):
+        a[k], _, _, a[s], _ = E.enc_conv3x3_norm(x0, E.pack_enc3(*_conv_w(g, 32, 32, 3, dev)), emit=True)
+    a["wpack"], a["bias"] = E.pack_enc3(*_conv_w(g, 64, 32, 3, dev))
+    a["dpack"], a["dbias"] = E.pack_enc1(*_conv_w(g, 64, 32, 1, dev))
+    return a
+
+
+def _encnorm_call(lgu, a):
+    out, r, kept, so, sr = lgu.encconv.enc_conv3x3_norm(a["x"], (a["wpack"], a["bias"]), stride=2, down=(a["dpack"], a["dbias"]),
+                                                        pre=("res_norm", a["stats_x"], a["y"], a["stats_y"]), keep=True, emit=True)
+    return out, r, kept, so.sum(2), sr.sum(2)     # which replica slot a block adds to is not fixed; the sums are exact
+
+
+case("encconv.enc_conv3x3_norm[res_norm, keep, emit]", ["lgu_encconv3x3_norm_h16"], "own", _encnorm_inputs, _encnorm_call,
+     dict(x=SAME, y=SAME, stats_x=SAME, stats_y=SAME, wpack=PACK, bias=SAME, dpack=PACK, dbias=SAME))
+case("encconv.stats_mean_rstd", ["lgu_encstats_finalize"], "own", _pick(_encnorm_inputs, "stats_x"),
+     lambda lgu, a: (lgu.encconv.stats_mean_rstd(a["stats_x"], _H * _W),), dict(stats_x=SAME))
+
+
+# ---- the Gaussian head: x is read with 16-byte loads, there is no element-wise twin -----------------------------------
+def _gh_inputs(half, x_half):
+    def build(dev):
+        import lgu_slam_amd as lgu
+        g = _gen(257)
+        with torch.random.fork_rng(devices=[]):      # the module draws its initial weights from torch's global generator
+            torch.manual_seed(257)
+            ga = lgu.GaussianMask(3, 7)
+        with torch.no_grad():
+            ga.meanMap.weight.copy_(torch.randn((2, 16), generator=g) * 0.3)
+        ga = ga.to(dev)
+        a = dict(x=_randn(g, (2, 3, 7, 256), dev, 0.5, torch.float16 if x_half else torch.float32))
+        a["wpack"], a["bias"] = lgu.gaussian_mask.pack_gaussian_head(ga.map, ga.meanMap, ga.covMap, half)
+        return a
+    return build
+
+
+for _half, _xh in ((False, False), (True, False), (True, True)):
+    case("gaussian_mask.gaussian_head[%s, %s x]" % ("half" if _half else "fp32", "h16" if _xh else "f32"), ["lgu_gaussian_head"], "own",
+         _gh_inputs(_half, _xh),
+         (lambda hf: lambda lgu, a: tuple(lgu.gaussian_mask.gaussian_head(a["x"], a["wpack"], a["bias"], half=hf, hidden=True)))(_half),
+         dict(x=A16("unsupported"), wpack=PACK, bias=SAME))
+
+
+# ---- the map export, the intake and the view: element accesses on every operand ---------------------------------------
+def _cloud_inputs(dev):
+    from tests import test_cloud as T
+    N, ht, wd = 8, 9, 13
+    poses, disps, intr, images = T.make_scene(100 * N + ht, N, ht, wd)
+    ix, th = T.entries(N)
+    a = dict(poses=_d(poses, dev), disps=_d(disps, dev), intrinsics=_d(intr, dev), ix=_d(ix, dev), thresh=_d(th, dev), images=_d(images, dev))
+    a["floor"] = (0.5 * a["disps"][a["ix"].clamp(0, N - 1)].mean(dim=[1, 2])).contiguous()
+    a["points"] = torch.full((ix.shape[0] * ht * wd, 3), 7.0, device=dev)        # room for every pixel: nothing is cut off
+    a["colors"] = torch.full((ix.shape[0] * ht * wd, 3), 7, dtype=torch.uint8, device=dev)
+    return a
+
+
+def _cloud_call(lgu, a):
+    p, c, o = lgu.cloud.point_cloud(a["poses"], a["disps"], a["intrinsics"], a["ix"], a["thresh"], a["images"], disp_floor=a["floor"],
+                                    color_dtype=torch.uint8, out=(a["points"], a["colors"]))
+    return p, c, o
+
+
+case("cloud.point_cloud[out]", ["lgu_cloud_decide_f32", "lgu_cloud_write_f32"], "own", _cloud_inputs, _cloud_call,
+     dict(poses=SAME, disps=SAME, intrinsics=SAME, ix=SAME, thresh=SAME, images=SAME, floor=SAME, points=SAME, colors=SAME),
+     inplace=("points", "colors"))
+
+
+def _intake_inputs(name):
+    def build(dev):
+        from tests import test_intake as T
+        seed, shape, _, _ = T.CASES[name]
+        import lgu_slam_amd as lgu
+        raw = torch.from_numpy(np.random.default_rng(seed).integers(0, 256, size=shape, dtype=np.uint8)).to(dev)
+        return dict(raw=raw, plan=T.make_plan(lgu, name))      # the plan keeps its camera table on the device once it was used
+    return build
+
+
+def _intake_call(name):
+    def call(lgu, a):
+        from tests import test_intake as T
+        return tuple(lgu.intake.frame(a["raw"], a["plan"], **T.CASES[name][3]))
+    return call
+
+
+for _name in ("tum5", "stereo", "table3"):      # one camera; two, in the block; three, in a device table
+    case("intake.frame[%s]" % _name, ["lgu_intake_frame_u8"], "own", _intake_inputs(_name), _intake_call(_name), dict(raw=SAME))
+
+
+def _depth_inputs(dev):
+    g = _gen(263)
+    raw = torch.rand((72, 104), generator=g) * 4000.0
+    raw[torch.rand((72, 104), generator=g) < 0.15] = 0.0
+    return dict(raw=raw.to(dev))
+
+
+def _depth_call(lgu, a):
+    from tests import test_intake as T
+    return (lgu.intake.sensor_disparity(a["raw"], lgu.intake.plan((72, 104), T._cam(72, 104), resize=(51, 75), crop=(0, 0, 48, 72))),)
+
+
+case("intake.sensor_disparity[f32]", ["lgu_intake_depth_f32"], "own", _depth_inputs, _depth_call, dict(raw=SAME))
+
+
+def _render_inputs(color_u8):
+    def build(dev):
+        g = _gen(269)
+        P = 300
+        pts = torch.randn((P, 3), generator=g) * 0.5 + torch.tensor([0.0, 0.0, 2.0])
+        col = torch.rand((P, 3), generator=g)
+        cams = torch.zeros((3, 7))
+        cams[:, :3] = torch.randn((3, 3), generator=g) * 0.2 + torch.tensor([0.0, 0.0, -1.0])
+        cams[:, 6] = 1.0
+        return dict(points=pts.to(dev), colors=((col * 255).to(torch.uint8) if color_u8 else col).to(dev),
+                    view=torch.tensor([0.05, -0.02, 0.3, 0.0, 0.0, 0.0, 1.0]).to(dev), intrinsics=torch.tensor([24.0, 24.0, 19.5, 14.5]).to(dev),
+                    cameras=cams.to(dev), image=torch.full((30, 40, 3), 7, dtype=torch.uint8, device=dev),
+                    depth=torch.full((30, 40), 7.0, device=dev))
+    return build
+
+
+for _u8 in (False, True):
+    case("render.render_view[%s colours]" % ("u8" if _u8 else "f32"), ["lgu_render_view"], "own", _render_inputs(_u8),
+         lambda lgu, a: tuple(lgu.render.render_view(a["points"], a["colors"], a["view"], a["intrinsics"], (30, 40), cameras=a["cameras"],
+                                                     camera_scale=0.2, out=(a["image"], a["depth"]))),
+         dict(points=SAME, colors=SAME, view=SAME, intrinsics=SAME, cameras=SAME, image=SAME, depth=SAME), inplace=("image", "depth"))
+
+
+# ======================================================================================================================
 # Entries with a pointer parameter that no case reaches, each with its reason
 # ======================================================================================================================
 EXCLUDED = {

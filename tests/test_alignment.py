@@ -55,15 +55,33 @@ def test_shift_table_is_the_issues():
 
 
 def pointer_entries():
-    """The lgu_* functions of include/lgu_corr.h that take at least one pointer other than the stream."""
+    """The lgu_* functions of include/lgu_corr.h that take at least one pointer other than the stream: as a parameter, or
+    as a field (a pointer, or an array of pointers) of an argument struct they take by value."""
     text = open(os.path.join(ROOT, "include", "lgu_corr.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    last = r"([A-Za-z_0-9]+)\s*(?:\[\d*\])?\s*$"
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{([^}]*)\}\s*(lgu_[a-z0-9_]+)\s*;", text):
+        structs[name] = [re.findall(last, d.strip())[0] for d in body.split(";") if "*" in d]
     out = {}
     for name, params in re.findall(r"\b(lgu_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        ptrs = [p for p in params.split(",") if ("*" in p or "[" in p) and not re.search(r"void\s*\*\s*stream\s*$", p.strip())]
-        if ptrs:
-            out[name] = [re.findall(r"([A-Za-z_0-9]+)\s*(?:\[\d*\])?\s*$", p.strip())[0] for p in ptrs]
+        names = []
+        for p in (q.strip() for q in params.split(",")):
+            by_value = re.match(r"(lgu_[a-z0-9_]+)\s+[A-Za-z_0-9]+$", p)
+            if by_value and by_value.group(1) in structs:
+                names += structs[by_value.group(1)]
+            elif ("*" in p or "[" in p) and not re.search(r"void\s*\*\s*stream\s*$", p):
+                names.append(re.findall(last, p)[0])
+        if names:
+            out[name] = names
     return out
+
+
+STRUCT_ARGS = ("lgu_flow_conv7_relu_h16", "lgu_conv3x3_c128_h16", "lgu_conv3x3_fanout_c128_h16", "lgu_head3x3_c128_h16",
+               "lgu_head3x3_pair_c128_h16", "lgu_gruconv3x3_c448_h16", "lgu_upmask1x1_c128_h16", "lgu_upmask_upsample_f32",
+               "lgu_conv1x1_o128_h16", "lgu_encconv3x3_h16", "lgu_encstem7x7_h16", "lgu_encout1x1_c128_h16", "lgu_encconv3x3_norm_h16",
+               "lgu_encstats_finalize", "lgu_gaussian_head", "lgu_cloud_decide_f32", "lgu_cloud_write_f32", "lgu_intake_frame_u8",
+               "lgu_intake_depth_f32", "lgu_render_view")
 
 
 def test_pointer_entries_parse_the_header():
@@ -71,6 +89,14 @@ def test_pointer_entries_parse_the_header():
     assert set(ents) <= set(declared_symbols())
     assert ents["lgu_corridx_fwd_f32"] == ["volume", "coords", "corr"]
     assert ents["lgu_image_normalize_u8"] == ["img", "out", "mean", "std"]
+    # entries that take a parameter block by value: its pointer fields, arrays of pointers and pointers to tables included
+    assert set(STRUCT_ARGS) <= set(ents) and len(STRUCT_ARGS) == 20
+    assert ents["lgu_conv3x3_c128_h16"] == ["x", "wpack", "bias", "out"]
+    assert ents["lgu_conv3x3_fanout_c128_h16"] == ["x", "wpack", "bias", "out"]
+    assert ents["lgu_head3x3_pair_c128_h16"] == ["x", "wpack", "bias", "out", "coords"]
+    assert ents["lgu_intake_frame_u8"] == ["raw", "image", "inputs", "cam_table"]
+    assert ents["lgu_encstats_finalize"] == ["acc", "mean_rstd"]
+    assert ents["lgu_render_view"] == ["points", "colors", "view", "intrinsics", "cameras", "scratch", "image", "depth"]
     for pure in ("lgu_version", "lgu_ba_build_slices", "lgu_offsets_finalize_scratch_bytes", "lgu_proximity_capacity",
                  "lgu_instnorm_resident_limit", "lgu_error_string"):
         assert pure not in ents
